@@ -6,10 +6,21 @@ device-resident synthetic series: differencing + Hannan-Rissanen init + the full
 Inputs are generated on the device before timing (ARIMAModel.sample semantics, Philox + Box-Muller, seed
 20261015, per-series jitter +-0.05 around ARIMASuite's [8.2, 0.2, 0.5, 0.3, 0.1]).
 
-Launch: python bench.py [--gpus N --steps K --warmup W]. With N > 1 and no torch.distributed environment, this
-process starts `torch.distributed.run` with N ranks (one per GPU) as a child before touching any GPU and exits
-with its status; under torch.distributed.run each rank fits its own contiguous series range (no data-path
+A plain run (python bench.py --gpus N --steps K --warmup W) does only what the headline figure needs: it samples the
+inputs, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given, and prints the result
+line (metric, value, unit, ms_per_step, dtype, the workload's config block). Everything else -- the default-options
+leg, the isolated launches behind the roofline block, the CPU baseline, the oracle parity of the timed step and the
+host-memory leg -- runs only with --full, where --default-leg, --cpu-seconds and --e2e select among them as before.
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]. With N > 1 and no
+torch.distributed environment, this process starts `torch.distributed.run` with N ranks (one per GPU) as a child
+before touching any GPU and exits with its status; under torch.distributed.run each rank fits its own contiguous series range (no data-path
 collective; gloo carries only the timing barrier and the max-over-ranks reduction).
+  --full            also run the secondary measurements and checks listed above (off by default)
+  --dump-outputs D  after the timed steps, write what the last timed step computed (the caller's result arrays) as
+                    D/<name>.npy in float64: at most DUMP_BYTES in all (over all ranks), a fixed seeded sample of the
+                    rows (rows.npy) when the arrays are larger; the inputs are seeded, so the same arguments give the
+                    same files
   --series S        series per GPU (weak scaling, default 1M: configs[1], and configs[2] read per GPU)
   --total-series S  fixed total over all GPUs (strong scaling: configs[2] = 8M series sharded over N GPUs)
   --smear 0|1       Breeze overlap reading at ARIMA.scala:526 (default 1)
@@ -80,6 +91,8 @@ PMC_TRAFFIC_FILE = os.path.join(ROOT, "tools", "pmc_traffic_c2.json")
 LIB_PATH = os.path.join(ROOT, "spark-timeseries_amd", "libsparkts_arima.so")
 SEED = 20261015
 ISO_STEPS = 3              # isolated launches behind roofline.launch_ms (their median)
+FULL_KEYS = ("roofline", "roofline_note", "parity", "cpu_baseline")
+DUMP_BYTES = 48_000_000    # --dump-outputs: the most it writes, all ranks together
 
 
 def build_sha():
@@ -327,6 +340,37 @@ def outputs_match(x, y):
     return ok
 
 
+def dump_rows(n, row_values, world=1):
+    """The rows --dump-outputs writes: all n when they fit into this rank's share of DUMP_BYTES (row_values float64
+    values per row, plus the row index), else a fixed sample of them (seeded, ascending)."""
+    import numpy as np
+    cap = DUMP_BYTES // max(world, 1) // (8 * (row_values + 1))
+    if n <= cap:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(SEED).choice(n, size=cap, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, outs, n, rank, world):
+    """--dump-outputs: the first n rows of the device tensors in outs (one row per series) as path/<name>.npy in
+    float64 (the integer outputs are exact in it), and the row indices they hold as path/rows.npy. With several
+    ranks every rank writes its own shard as <name>.rank<r>.npy, within DUMP_BYTES / world."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows = dump_rows(n, sum(v.numel() // max(len(v), 1) for v in outs.values()), world)
+    idx = torch.from_numpy(rows).to(next(iter(outs.values())).device)
+    tag = "" if world == 1 else f".rank{rank}"
+    np.save(os.path.join(path, f"rows{tag}.npy"), rows.astype(np.float64))
+    for name, v in outs.items():
+        np.save(os.path.join(path, f"{name}{tag}.npy"), v[:n][idx].cpu().numpy().astype(np.float64))
+
+
+def result_line(line, full):
+    """The JSON line of the order-search and autoFit configs: a plain run prints the headline only, without the keys
+    that the --full measurements fill."""
+    return json.dumps(line if full else {k: v for k, v in line.items() if k not in FULL_KEYS})
+
+
 def oracle_row_parity(res, exp):
     """Rows of the timed step bit-identical to the oracle (status, n_eval, n_grad exact; coef, LL and flags bit for
     bit where the fit returned normally, NaN coefficients where it failed): the count of matching rows."""
@@ -385,6 +429,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 20 for c2/c3, 5 for c4, 2 for c5)")
     ap.add_argument("--warmup", type=int, default=None, help="untimed warmup steps (default: 3; 1 for c5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the default-options leg, the isolated launches (roofline), the CPU baseline, the "
+                         "oracle parity and the host-memory leg (--default-leg, --cpu-seconds, --e2e select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
     ap.add_argument("--series", type=int, default=0, help="series per GPU (weak scaling; 0: 1M, 10 000 for c1)")
     ap.add_argument("--total-series", type=int, default=0, help="fixed total series over all GPUs (strong scaling)")
@@ -480,7 +529,7 @@ def main():
     # the drop-in as a caller gets it: ABI defaults in a child process that keeps the box's
     # hardware-queue setting, run to completion BEFORE this process touches the GPU
     default_leg = None
-    if args.config == "c2" and world == 1 and args.default_leg:
+    if args.full and args.config == "c2" and world == 1 and args.default_leg:
         default_leg = run_default_leg(args)
     import sparkts_amd._lib as L
     dev = torch.device("cuda", dev_id)
@@ -539,8 +588,48 @@ def main():
     log(f"[rank {rank}] {args.steps} steps in {elapsed:.3f} s; last step: difference {s0['ms_difference']:.1f} ms, "
         f"hr {s0['ms_hr_init']:.1f} ms, cg {s0['ms_cg_fit']:.1f} ms")
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[(calls[0] - 1) % len(outs)], N, rank, world)
     st_h = outs[(calls[0] - 1) % len(outs)]["status"].cpu().numpy()
     conv = float((st_h == 0).mean()) if N else 1.0
+    # the headline: all a plain run prints
+    head = {
+        "metric": METRICS.get(args.config, f"series fitted/sec, {args.config}"),
+        "value": total_series * args.steps / elapsed,
+        "unit": "series fitted/sec",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": f"synthetic: ARIMAModel.sample semantics on device, seed {SEED}, coef jitter +-{jitter}",
+        "config": {"workload": f"ARIMA({p},{d},{q}){'+c' if I else ''} css-cgd, "
+                               + (f"{total_series} series total over {world} GPU(s)" if scaling == "strong"
+                                  else f"{N} series x {T} pts per GPU")
+                               + {"c1": " (BASELINE.json configs[0])", "c4": " (BASELINE.json configs[3])"}.get(
+                                   args.config, " (BASELINE.json configs[1]/[2])"),
+                   "series_per_gpu": N, "series_total": total_series, "series_len": T,
+                   "parallelism": f"series-sharded x{world}, no collective",
+                   "breeze_overlap": "smear" if args.smear else "shift",
+                   "fit_kernel": "k_cg_fit (LDS slots, 1 wave/SIMD)", "fit_pipeline": args.pipeline,
+                   "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
+                   "converged_fraction": conv, "series_done": s0["series_done"],
+                   "mean_n_eval": s0["n_eval"] / max(N, 1), "mean_n_grad": s0["n_grad"] / max(N, 1),
+                   "lane_f_passes_per_series": s0["f_passes"] / max(N, 1),
+                   "lane_g_passes_per_series": s0["g_passes"] / max(N, 1),
+                   "kernel_ms": {"difference": s0["ms_difference"], "hr_init": s0["ms_hr_init"],
+                                 "cg_fit": s0["ms_cg_fit"]}},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
     n = T - d
     M = max(p, q)
     S = n - M
@@ -616,35 +705,8 @@ def main():
         pmc, pmc_key = pmc_traffic({"series": N, "T": T, "p": p, "d": d, "q": q, "I": int(I), "smear": args.smear,
                                     "fit_kernel": 0,
                                     "options": os.environ.get("SPARKTS_OPTIONS", "")}, sha)
-        result = {
-            "metric": METRICS.get(args.config, f"series fitted/sec, {args.config}"),
-            "value": total_series * args.steps / elapsed,
-            "unit": "series fitted/sec",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": f"synthetic: ARIMAModel.sample semantics on device, seed {SEED}, coef jitter +-{jitter}",
-            "config": {"workload": f"ARIMA({p},{d},{q}){'+c' if I else ''} css-cgd, "
-                                   + (f"{total_series} series total over {world} GPU(s)" if scaling == "strong"
-                                      else f"{N} series x {T} pts per GPU")
-                                   + {"c1": " (BASELINE.json configs[0])", "c4": " (BASELINE.json configs[3])"}.get(
-                                       args.config, " (BASELINE.json configs[1]/[2])"),
-                       "series_per_gpu": N, "series_total": total_series, "series_len": T,
-                       "parallelism": f"series-sharded x{world}, no collective",
-                       "breeze_overlap": "smear" if args.smear else "shift",
-                       "fit_kernel": "k_cg_fit (LDS slots, 1 wave/SIMD)", "fit_pipeline": args.pipeline,
-                       "hw_queues": int(os.environ.get("GPU_MAX_HW_QUEUES", "4")),
-                       "converged_fraction": conv, "series_done": s0["series_done"],
-                       "mean_n_eval": s0["n_eval"] / max(N, 1), "mean_n_grad": s0["n_grad"] / max(N, 1),
-                       "lane_f_passes_per_series": s0["f_passes"] / max(N, 1),
-                       "lane_g_passes_per_series": s0["g_passes"] / max(N, 1),
-                       "kernel_ms": {"difference": s0["ms_difference"], "hr_init": s0["ms_hr_init"],
-                                     "cg_fit": s0["ms_cg_fit"]}},
+        result = dict(head)
+        result.update({
             "roofline": {"bound": "fp64-valu", "kernel": "k_cg_fit", "achieved": achieved_tf,
                          "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved_tf / FP64_PEAK_TFLOPS,
                          "launch_ms": cg_ms, "launch_ms_each": iso_ms,
@@ -681,7 +743,7 @@ def main():
                          "wave_passes": {"f": s0["wave_f_passes"], "g": s0["wave_g_passes"],
                                          "multi": s0["wave_multi_passes"]}},
             "cpu_baseline": cpu,
-        }
+        })
         if default_leg is not None:
             result["default_config"] = default_leg
         if e2e is not None:
@@ -729,6 +791,8 @@ def run_c5(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist if world > 1 else None)
     st = eng.stats()                      # the last search: counter sums and algorithmic flops over its 216 fits
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dict(order=order, coef=coef, aic=aic), N, rank, world)
     o = order[:N].cpu().numpy()
     found = float((o[:, 0] >= 0).mean()) if N else 1.0
     if rank == 0:
@@ -763,13 +827,13 @@ def run_c5(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
             "hbm_frac_pmc": (pmc["hbm_bytes_per_step"] / (search_ms * 1e-3) / 1e9 / HBM_PEAK_GBS)
             if pmc and search_ms else None})
         cpu, parity = None, None
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             cpu, parity = c5_cpu_baseline(series, o, coef, aic, T, args.smear)
         sel = {}
         for r in o[: min(N, 65536)]:
             key = f"({r[0]},{r[1]},{r[2]}){'+c' if r[3] == 1 else ''}" if r[0] >= 0 else "none"
             sel[key] = sel.get(key, 0) + 1
-        print(json.dumps({
+        print(result_line({
             "metric": "series searched/sec, ARIMA order search p,q<=5 d<=2 +-c (216 CSS-CGD fits/series, min approxAIC), "
                       "x 1024 pts",
             "value": total_series * args.steps / elapsed, "unit": "series searched/sec", "n_gpus": world,
@@ -791,7 +855,7 @@ def run_c5(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
             "roofline": roofline,
             "roofline_note": "per grid point (flops, evaluations, MaxEval fraction): tools/grid_profile.py",
             "parity": parity,
-            "cpu_baseline": cpu}), flush=True)
+            "cpu_baseline": cpu}, args.full), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -825,10 +889,12 @@ def run_af(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
     torch.cuda.synchronize(dev)
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0, dist if world > 1 else None)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, N, rank, world)
     res = {k: v[:N].cpu().numpy() for k, v in out.items()}
     fits = int(res["n_fits"].sum())
     cpu, rows_checked, rows_ok = None, 0, 0
-    if args.cpu_seconds > 0 and N > 0:
+    if args.full and args.cpu_seconds > 0 and N > 0:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
         affinity = len(os.sched_getaffinity(0))
@@ -861,7 +927,7 @@ def run_af(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
         for r in res["order"][: min(N, 65536)]:
             key = f"({r[0]},{r[1]},{r[2]}){'+c' if r[3] == 1 else ''}" if r[0] >= 0 else "none"
             sel[key] = sel.get(key, 0) + 1
-        print(json.dumps({
+        print(result_line({
             "metric": "series auto-fitted/sec, ARIMA.autoFit (KPSS d <= 2, stepwise p, q <= 5, css-cgd), x 1024 pts",
             "value": total_series * args.steps / elapsed, "unit": "series auto-fitted/sec", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
@@ -879,7 +945,7 @@ def run_af(args, eng, series, N, T, total_series, world, rank, dev, barrier, dis
             "parity": {"oracle_rows": par["oracle_rows"], "bit_identical": par["bit_identical"],
                        "every_rank_bit_identical": par["every_rank_bit_identical"], "ranks_checked": par["ranks"],
                        "checked": "status, (p, d, q, intercept), n_fits, coefficients and approxAIC, bit for bit"},
-            "cpu_baseline": cpu}), flush=True)
+            "cpu_baseline": cpu}, args.full), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

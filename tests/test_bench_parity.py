@@ -66,3 +66,46 @@ def test_oracle_row_parity_counts_rows(bench):
     res["coef"][2, 1] = 0.0                                          # a failed fit must report NaN coefficients
     res["n_grad"][3] += 1
     assert bench.oracle_row_parity(res, exp) == 1
+
+
+def test_dump_rows_is_every_row_or_a_fixed_sample_within_the_limit(bench):
+    values = 10                                       # C2: 5 coefficients + LL, status, n_eval, n_grad, flags
+    cap = bench.DUMP_BYTES // (8 * (values + 1))
+    assert bench.DUMP_BYTES <= 64_000_000
+    assert np.array_equal(bench.dump_rows(cap, values), np.arange(cap))
+    rows = bench.dump_rows(1 << 20, values)
+    assert len(rows) == cap < 1 << 20 and len(rows) * 8 * (values + 1) <= bench.DUMP_BYTES
+    assert (np.diff(rows) > 0).all() and rows[0] >= 0 and rows[-1] < 1 << 20
+    assert np.array_equal(rows, bench.dump_rows(1 << 20, values))      # the same sample in every run
+    assert len(bench.dump_rows(1 << 20, values, world=8)) == cap // 8   # the limit holds over all ranks together
+
+
+def test_dump_outputs_writes_float64_arrays_of_the_first_n_rows(bench, tmp_path):
+    outs = _outs(n=7)
+    outs["coef"][2, 1] = float("nan")
+    bench.dump_outputs(str(tmp_path / "d"), outs, 6, 0, 1)
+    assert sorted(os.listdir(tmp_path / "d")) == sorted(f"{k}.npy" for k in list(outs) + ["rows"])
+    assert np.array_equal(np.load(tmp_path / "d" / "rows.npy"), np.arange(6, dtype=np.float64))
+    for k, v in outs.items():
+        a = np.load(tmp_path / "d" / f"{k}.npy")
+        assert a.dtype == np.float64 and a.shape == tuple(v[:6].shape)
+        assert np.array_equal(a, v[:6].numpy().astype(np.float64), equal_nan=True)
+    bench.dump_outputs(str(tmp_path / "d"), outs, 6, 1, 2)             # several ranks: one set of files per rank
+    assert os.path.exists(tmp_path / "d" / "coef.rank1.npy")
+
+
+def test_dump_outputs_samples_rows_when_the_arrays_exceed_the_limit(bench, tmp_path, monkeypatch):
+    n, values = 500, 10
+    outs = _outs(n=n + 3)
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 120 * 8 * (values + 1))     # room for 120 rows on each of 2 ranks
+    bench.dump_outputs(str(tmp_path), outs, n, 1, 2)
+    rows = np.load(tmp_path / "rows.rank1.npy")
+    assert rows.dtype == np.float64 and len(rows) == 120 and (np.diff(rows) > 0).all() and rows[-1] < n
+    idx = rows.astype(np.int64)
+    assert np.array_equal(idx, bench.dump_rows(n, values, 2))
+    total = rows.nbytes
+    for k, v in outs.items():
+        a = np.load(tmp_path / f"{k}.rank1.npy")
+        assert a.dtype == np.float64 and np.array_equal(a, v.numpy()[idx].astype(np.float64))
+        total += a.nbytes
+    assert 2 * total <= bench.DUMP_BYTES

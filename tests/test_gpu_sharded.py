@@ -57,7 +57,7 @@ def test_bench_two_ranks_on_one_gpu_checks_every_rank_against_the_oracle():
     # shard with the oracle and the verdicts meet in gloo reductions (here: 2 ranks sharing GPU 0)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "0", "--series", "16384",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--device", "0", "--series", "16384",
            "--steps", "2", "--warmup", "1", "--e2e", "1", "--cpu-seconds", "2", "--pipeline", "2"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -82,7 +82,7 @@ def test_bench_autofit_two_ranks_on_one_gpu_checks_every_rank():
     # with oracle.autofit; the verdicts meet in the gloo reductions
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     env.pop("WORLD_SIZE", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--device", "0", "--config", "af",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--device", "0", "--config", "af",
            "--series", "1024", "--steps", "1", "--warmup", "0", "--cpu-seconds", "4"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]

@@ -4,8 +4,8 @@
 set -o pipefail
 OUT=gpurun_out/${TAG:-r03/ab_lib}
 mkdir -p $OUT
-ISO="python bench.py --steps 2 --warmup 1 --pipeline 1 --e2e 0 --cpu-seconds 0"
-PIPE="python bench.py --steps 20 --warmup 5 --e2e 0 --cpu-seconds 0"
+ISO="python bench.py --full --steps 2 --warmup 1 --pipeline 1 --e2e 0 --cpu-seconds 0"
+PIPE="python bench.py --full --steps 20 --warmup 5 --e2e 0 --cpu-seconds 0"
 for r in $(seq 1 ${ROUNDS:-2}); do
   for lib in ${LIBS:-oldsel newsel}; do
     L=$PWD/spark-timeseries_amd/libsparkts_arima_dev_$lib.so
