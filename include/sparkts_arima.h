@@ -198,6 +198,32 @@ int arima_forecast_batch(arima_handle *h, const double *series, int64_t n_series
 int arima_forecast_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
                                 int32_t p, int32_t d, int32_t q, int32_t include_intercept, const double *d_coef,
                                 int32_t n_future, double *d_out, int64_t ld_out, void *stream);
+/* ---- the TimeSeriesModel pair of ARIMAModel (TimeSeriesModel.scala:23-45), N x T in, N x T out ---------------- *
+ * ARIMAModel.removeTimeDependentEffects (ARIMA.scala:629-644): the residuals of each series under its model --
+ * differencesOfOrderD(ts, d) (size-preserving, nothing dropped), then iterateARMA with op = - whose errors are its own
+ * output. What lbtest / dwtest / bgtest (TimeSeriesStatisticalTests.scala:251-320) take as input.
+ * ARIMAModel.addTimeDependentEffects (ARIMA.scala:655-667): each model driven by the caller's innovations (`noise`)
+ * -- iterateARMA with op = + on its own output, then inverseDifferencesOfOrderD(_, d); `sample` (:675-678) is this
+ * over Gaussian noise.
+ * coef N x k. T < d returns ARIMA_E_INVALID_ARG; N == 0 or T == 0 return ARIMA_OK and write nothing. One streaming
+ * pass (p, q <= 5 and d <= 8: the tiled kernel; every other accepted order: the runtime-order kernel).
+ * `out` may be exactly the input (the reference's sample calls addTimeDependentEffects(vec, vec)): the same pointer
+ * and, for the device entry points, the same stride; any other overlap of the two ranges, or of out and coef,
+ * returns ARIMA_E_INVALID_ARG. Nothing is written beyond column T of a row.                                        */
+int arima_remove_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                               int32_t p, int32_t d, int32_t q, int32_t include_intercept, const double *coef,
+                               double *out);
+int arima_add_effects_batch(arima_handle *h, const double *noise, int64_t n_series, int32_t T,
+                            int32_t p, int32_t d, int32_t q, int32_t include_intercept, const double *coef,
+                            double *out);
+/* Same, device-resident: d_series / d_noise N x T (row stride ld >= T), d_coef N x k, d_out N x T (row stride
+ * ld_out >= T) */
+int arima_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                      int64_t ld, int32_t p, int32_t d, int32_t q, int32_t include_intercept,
+                                      const double *d_coef, double *d_out, int64_t ld_out, void *stream);
+int arima_add_effects_batch_device(arima_handle *h, const double *d_noise, int64_t n_series, int32_t T,
+                                   int64_t ld, int32_t p, int32_t d, int32_t q, int32_t include_intercept,
+                                   const double *d_coef, double *d_out, int64_t ld_out, void *stream);
 /* ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815) for N coefficient rows, flags_out N */
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t n_series, int32_t p, int32_t q,
                             int32_t include_intercept, uint8_t *flags_out);

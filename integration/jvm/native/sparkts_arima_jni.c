@@ -7,7 +7,8 @@
  * (hence `_00024` in the symbol names).
  *
  * Replaces, per call: ARIMA.fitModel over a bucket of equal-length series (ARIMA.scala:79-116),
- * ARIMAModel.forecast (ARIMA.scala:696-764) and the order-search grid (ARIMA.scala:280-375, 826-830).
+ * ARIMAModel.forecast (ARIMA.scala:696-764), removeTimeDependentEffects / addTimeDependentEffects (ARIMA.scala:629-667)
+ * and the order-search grid (ARIMA.scala:280-375, 826-830).
  */
 #include <jni.h>
 #include <stdint.h>
@@ -62,6 +63,24 @@ JNIEXPORT jint JNICALL JNI_FN(forecastBatch)(JNIEnv *env, jobject self, jlong h,
     return arima_forecast_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t, p, d, q,
                                 intercept ? 1 : 0, (const double *)BUF(env, coef), nFuture,
                                 (double *)BUF(env, out));
+}
+
+/* arima_remove_effects_batch / arima_add_effects_batch (ARIMAModel.removeTimeDependentEffects, ARIMA.scala:629-644;
+ * addTimeDependentEffects, :655-667): series / noise N x T, coef N x k, out N x T (out may be the input buffer) */
+JNIEXPORT jint JNICALL JNI_FN(removeEffectsBatch)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,
+                                                  jint p, jint d, jint q, jboolean intercept, jobject coef,
+                                                  jobject out) {
+    (void)self;
+    return arima_remove_effects_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t, p, d, q,
+                                      intercept ? 1 : 0, (const double *)BUF(env, coef), (double *)BUF(env, out));
+}
+
+JNIEXPORT jint JNICALL JNI_FN(addEffectsBatch)(JNIEnv *env, jobject self, jlong h, jobject noise, jlong n, jint t,
+                                               jint p, jint d, jint q, jboolean intercept, jobject coef,
+                                               jobject out) {
+    (void)self;
+    return arima_add_effects_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, noise), n, t, p, d, q,
+                                   intercept ? 1 : 0, (const double *)BUF(env, coef), (double *)BUF(env, out));
 }
 
 /* arima_order_search_batch: series N x T, order N x 4, coef N x 11, aic N */

@@ -11,6 +11,9 @@
  *                                              JavaTimeSeriesRDD.scala:124-133), batched per partition
  *   ArimaMI355X.forecastMany / orderSearchMany batched ARIMAModel.forecast (ARIMA.scala:696-764) and the
  *                                              min-approxAIC order grid (ARIMA.scala:280-375, 826-830)
+ *   ArimaMI355X.removeTimeDependentEffectsMany / addTimeDependentEffectsMany
+ *                                              batched ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects
+ *                                              (ARIMA.scala:629-644, :655-667): residuals and model application
  *   ArimaMI355X.autoFit / autoFitMany          drop-in for ARIMA.autoFit (ARIMA.scala:280-375): KPSS choice of d,
  *                                              stepwise walk with the css-bobyqa retry, batched per partition
  *   method = "css-bobyqa"                      fitWithCSSBOBYQA (ARIMA.scala:130-160) on the device
@@ -39,6 +42,10 @@ object ArimaMI355XNative {
                        flags: ByteBuffer): Int
   @native def forecastBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, p: Int, d: Int, q: Int,
                             intercept: Boolean, coef: DoubleBuffer, nFuture: Int, out: DoubleBuffer): Int
+  @native def removeEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, p: Int, d: Int, q: Int,
+                                 intercept: Boolean, coef: DoubleBuffer, out: DoubleBuffer): Int
+  @native def addEffectsBatch(handle: Long, noise: DoubleBuffer, n: Long, t: Int, p: Int, d: Int, q: Int,
+                              intercept: Boolean, coef: DoubleBuffer, out: DoubleBuffer): Int
   @native def orderSearch(handle: Long, series: DoubleBuffer, n: Long, t: Int, maxP: Int, maxD: Int, maxQ: Int,
                           interceptMode: Int, method: Int, order: IntBuffer, coef: DoubleBuffer,
                           aic: DoubleBuffer): Int
@@ -169,6 +176,37 @@ object ArimaMI355X {
       coef, nFuture, out), "arima_forecast_batch")
     Array.tabulate(n)(i => Array.tabulate(t + nFuture)(j => out.get(i * (t + nFuture) + j)))
   }
+
+  private def effectsMany(model: ARIMAModel, values: Array[Array[Double]], add: Boolean): Array[Array[Double]] = {
+    val n = values.length
+    val t = if (n == 0) 0 else values(0).length
+    require(values.forall(_.length == t), "one call takes series of equal length (bucket by length)")
+    val k = model.coefficients.length
+    val rows = doubles(math.max(n.toLong * t, 1L))
+    values.foreach(v => rows.put(v))
+    rows.flip()
+    val coef = doubles(math.max(n.toLong * k, 1L))
+    (0 until n).foreach(_ => coef.put(model.coefficients))
+    coef.flip()
+    val out = doubles(math.max(n.toLong * t, 1L))
+    if (add) {
+      check(ArimaMI355XNative.addEffectsBatch(handle, rows, n, t, model.p, model.d, model.q, model.hasIntercept,
+        coef, out), "arima_add_effects_batch")
+    } else {
+      check(ArimaMI355XNative.removeEffectsBatch(handle, rows, n, t, model.p, model.d, model.q, model.hasIntercept,
+        coef, out), "arima_remove_effects_batch")
+    }
+    Array.tabulate(n)(i => Array.tabulate(t)(j => out.get(i * t + j)))
+  }
+
+  /** Batched ARIMAModel.removeTimeDependentEffects (ARIMA.scala:629-644): the residuals of every series under
+    * `model`, N x T -- the input of lbtest / dwtest / bgtest (TimeSeriesStatisticalTests.scala:251-320). */
+  def removeTimeDependentEffectsMany(model: ARIMAModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    effectsMany(model, values, add = false)
+
+  /** Batched ARIMAModel.addTimeDependentEffects (ARIMA.scala:655-667): `model` driven by each row of innovations. */
+  def addTimeDependentEffectsMany(model: ARIMAModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    effectsMany(model, values, add = true)
 
   /** Drop-in for ARIMA.autoFit (ARIMA.scala:280-304): one series, the reference's exceptions. maxP <= 8 (its
     * css-bobyqa retries have at most 11 parameters). */

@@ -457,6 +457,60 @@ __global__ __launch_bounds__(64) void k_gen_forecast(const double *__restrict__ 
     }
 }
 
+// ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects (ARIMA.scala:629-644, :655-667) at runtime orders,
+// d <= kGenMaxD: k_effects' recurrences (arima_effects.hip) with the state in private arrays -- d differencing values
+// or running sums, max(p, q) history values and the errors (under updateMAErrors' smear, ARIMA.scala:544-554, every
+// lag past the first holds the error before the last: two values). No workspace; the lane reads element t before it
+// writes it, so the output may be the input (no __restrict__ on the rows).
+constexpr int kGenMaxD = 16;
+
+__global__ __launch_bounds__(64) void k_gen_effects(const double *in_all, int64_t ld_in,
+                                                    const double *__restrict__ coef_all, int k, double *out_all,
+                                                    int64_t ld_out, int64_t N, int T, int p, int d, int q, int I,
+                                                    int add) {
+    const int64_t sid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (sid >= N) return;
+    const double *in = in_all + sid * ld_in;
+    const double *coef = coef_all + sid * k;
+    double *out = out_all + sid * ld_out;
+    double c[kGenMaxK];
+    for (int j = 0; j < kGenMaxK; ++j) c[j] = j < k ? coef[j] : 0.0;
+    const double ic = (double)I * c[0];
+    const double ia = I ? c[0] : 0.0;
+    double hist[kGenMaxOrder], lv[kGenMaxD];
+    for (int j = 0; j < kGenMaxOrder; ++j) hist[j] = ia;
+    for (int r = 0; r < kGenMaxD; ++r) lv[r] = 0.0;
+    double e1 = 0.0, e2 = 0.0;                                                          // ma[0], ma[1..q)
+    for (int t = 0; t < T; ++t) {
+        const double v = in[t];
+        double x = v, w;
+        if (!add) {
+            for (int r = 1; r <= d; ++r) {                                              // differencesOfOrderD column t
+                const double nx = t < r ? x : x - lv[r - 1];
+                lv[r - 1] = x;
+                x = nx;
+            }
+            w = x - ic;
+            for (int j = 0; j < p; ++j) w = w - hist[j] * c[I + j];
+            for (int j = 0; j < q; ++j) w = w - (j == 0 ? e1 : e2) * c[I + p + j];
+        } else {
+            w = v + ic;
+            for (int j = 0; j < p; ++j) w = w + hist[j] * c[I + j];
+            for (int j = 0; j < q; ++j) w = w + (j == 0 ? e1 : e2) * c[I + p + j];
+        }
+        e2 = e1;
+        e1 = add ? v : w;
+        for (int j = p - 1; j >= 1; --j) hist[j] = hist[j - 1];
+        if (p > 0) hist[0] = add ? w : x;
+        if (add)
+            for (int l = d; l >= 1; --l) {                                              // inverseDifferencesOfOrderD
+                w = t < l ? w : w + lv[l - 1];
+                lv[l - 1] = w;
+            }
+        out[t] = w;
+    }
+}
+
 // =======================================================================================================
 // launchers (orders up to kGenMaxOrder; arima_launch.hpp)
 // =======================================================================================================
@@ -537,6 +591,17 @@ int launch_gen_forecast(const double *ts, int64_t ld_in, const double *coef, int
     if (N == 0) return ARIMA_OK;
     hipLaunchKernelGGL(k_gen_forecast, dim3(gen_grid(N, 64)), dim3(64), 0, s, ts, ld_in, coef, k, out, ld_out, N, T, p,
                        d, q, I, n_future, ws, ws_stride);
+    STS_GEN_CHECK();
+    return ARIMA_OK;
+}
+
+int launch_gen_effects(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out,
+                       int64_t N, int T, int p, int d, int q, int I, int add, hipStream_t s) {
+    if (N == 0 || T == 0) return ARIMA_OK;
+    if (!gen_orders_ok(p, q) || d < 0 || d > kGenMaxD) return ARIMA_E_UNSUPPORTED;
+    if (T < d || k != I + p + q || ld_in < T || ld_out < T) return ARIMA_E_INVALID_ARG;
+    hipLaunchKernelGGL(k_gen_effects, dim3(gen_grid(N, 64)), dim3(64), 0, s, in, ld_in, coef, k, out, ld_out, N, T, p,
+                       d, q, I, add);
     STS_GEN_CHECK();
     return ARIMA_OK;
 }

@@ -25,6 +25,10 @@ int launch_forecast(const double *ts, int64_t ld_in, const double *coef, int k, 
                     int64_t N, int T, int p, int d, int q, int I, int n_future, hipStream_t s);
 int launch_inverse_difference(const double *in, int64_t ld_in, double *out, int64_t ld_out, int64_t N, int T,
                               int d, hipStream_t s);
+// ARIMAModel.removeTimeDependentEffects (add == 0) / addTimeDependentEffects (add == 1), p, q <= 5, d <= 8
+// (arima_effects.hip); out may be exactly in (same stride)
+int launch_effects(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out, int64_t N,
+                   int T, int p, int d, int q, int I, int add, hipStream_t s);
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.
@@ -156,5 +160,8 @@ int64_t gen_forecast_ws_doubles(int T, int p, int d, int q, int n_future);
 int launch_gen_forecast(const double *ts, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out,
                         int64_t N, int T, int p, int d, int q, int I, int n_future, double *ws, int64_t ws_stride,
                         hipStream_t s);
+// launch_effects at any order the library accepts (p, q <= kGenMaxOrder, d <= 16); no workspace
+int launch_gen_effects(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out,
+                       int64_t N, int T, int p, int d, int q, int I, int add, hipStream_t s);
 
 }  // namespace sts

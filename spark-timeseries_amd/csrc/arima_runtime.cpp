@@ -1540,6 +1540,95 @@ int arima_forecast_batch_device(arima_handle *h, const double *d_series, int64_t
     return ARIMA_OK;
 }
 
+// ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects over a device batch: k_effects (p, q <= 5, d <= 8,
+// the tiled streaming kernel) or the runtime-order k_gen_effects for every other order
+static int effects_any(const double *in, int64_t ld, const double *coef, int k, double *out, int64_t ld_out,
+                       int64_t N, int T, int p, int d, int q, int I, int add, hipStream_t s) {
+    if (!sts::gen_order(p, q) && d <= 8)
+        return sts::launch_effects(in, ld, coef, k, out, ld_out, N, T, p, d, q, I, add, s);
+    return sts::launch_gen_effects(in, ld, coef, k, out, ld_out, N, T, p, d, q, I, add, s);
+}
+
+static bool spans_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a_bytes > 0 && b_bytes > 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+static int effects_host(arima_handle *h, const double *in, int64_t N, int32_t T, int32_t p, int32_t d, int32_t q,
+                        int32_t I, const double *coef, double *out, int add) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    if (N < 0 || T < d) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0 || T == 0) return ARIMA_OK;
+    const int k = I + p + q;
+    if (!in || (!coef && k > 0) || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t row_bytes = (size_t)N * T * sizeof(double);
+    if ((out != in && spans_meet(in, row_bytes, out, row_bytes)) ||
+        spans_meet(coef, (size_t)N * k * sizeof(double), out, row_bytes))
+        return set_err(h, ARIMA_E_INVALID_ARG, "out overlaps an input");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, in, row_bytes, hipMemcpyHostToDevice, s));
+    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
+    // in place on the staged rows: every wave reads a tile before it writes it
+    RCCHK(h, effects_any(h->h_series.as<double>(), T, h->h_coef.as<double>(), k, h->h_series.as<double>(), T, N, T, p,
+                         d, q, I, add, s), "effects");
+    HIPCHK(h, hipMemcpyAsync(out, h->h_series.ptr, row_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+static int effects_device(arima_handle *h, const double *d_in, int64_t N, int32_t T, int64_t ld, int32_t p, int32_t d,
+                          int32_t q, int32_t I, const double *d_coef, double *d_out, int64_t ld_out, void *stream,
+                          int add) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    if (N < 0 || T < d || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0 || T == 0) return ARIMA_OK;
+    const int k = I + p + q;
+    if (!d_in || (!d_coef && k > 0) || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t in_bytes = ((size_t)(N - 1) * ld + T) * sizeof(double);
+    const size_t out_bytes = ((size_t)(N - 1) * ld_out + T) * sizeof(double);
+    const bool in_place = d_out == d_in && ld_out == ld;
+    if ((!in_place && spans_meet(d_in, in_bytes, d_out, out_bytes)) ||
+        spans_meet(d_coef, (size_t)N * k * sizeof(double), d_out, out_bytes))
+        return set_err(h, ARIMA_E_INVALID_ARG, "out overlaps an input");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    begin_call(h, s);
+    RCCHK(h, effects_any(d_in, ld, d_coef, k, d_out, ld_out, N, T, p, d, q, I, add, s), "effects");
+    HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
+}
+
+int arima_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p, int32_t d,
+                               int32_t q, int32_t I, const double *coef, double *out) {
+    return effects_host(h, series, N, T, p, d, q, I, coef, out, 0);
+}
+
+int arima_add_effects_batch(arima_handle *h, const double *noise, int64_t N, int32_t T, int32_t p, int32_t d,
+                            int32_t q, int32_t I, const double *coef, double *out) {
+    return effects_host(h, noise, N, T, p, d, q, I, coef, out, 1);
+}
+
+int arima_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                      int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef, double *d_out,
+                                      int64_t ld_out, void *stream) {
+    return effects_device(h, d_series, N, T, ld, p, d, q, I, d_coef, d_out, ld_out, stream, 0);
+}
+
+int arima_add_effects_batch_device(arima_handle *h, const double *d_noise, int64_t N, int32_t T, int64_t ld,
+                                   int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef, double *d_out,
+                                   int64_t ld_out, void *stream) {
+    return effects_device(h, d_noise, N, T, ld, p, d, q, I, d_coef, d_out, ld_out, stream, 1);
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // order search over (d, p, q, intercept) — SURVEY.md 8(f) row 2 (config C5)
 // ---------------------------------------------------------------------------------------------------------

@@ -4,6 +4,6 @@ Host-side mirror of the reference's Python API (python/sparkts/) over the C ABI 
 """
 from . import _lib  # noqa: F401
 from .models import ARIMA  # noqa: F401
-from .timeseriesrdd import fit_arima_partition, map_series_fit_arima  # noqa: F401
+from .timeseriesrdd import arima_residuals_partition, fit_arima_partition, map_series_fit_arima  # noqa: F401
 
 __version__ = "0.1.0"

@@ -52,7 +52,8 @@ EXPORTED = [
     "arima_css_gradient_batch", "arima_hannan_rissanen_batch", "arima_forecast_batch", "arima_model_flags_batch",
     "arima_sample_batch_device", "arima_order_search_batch", "arima_order_search_batch_device",
     "arima_forecast_batch_device", "arima_synchronize", "arima_autofit_batch", "arima_autofit_batch_device",
-    "arima_kpss_batch",
+    "arima_kpss_batch", "arima_remove_effects_batch", "arima_remove_effects_batch_device",
+    "arima_add_effects_batch", "arima_add_effects_batch_device",
 ]
 
 
@@ -149,6 +150,10 @@ def load():
         L.arima_autofit_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                                                  _vp]
         L.arima_kpss_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i32p]
+        for fn in (L.arima_remove_effects_batch, L.arima_add_effects_batch):
+            fn.argtypes = [H, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _dp, _dp]
+        for fn in (L.arima_remove_effects_batch_device, L.arima_add_effects_batch_device):
+            fn.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]
         _lib = L
         return L
 
@@ -318,6 +323,48 @@ class Engine:
         self._check(self.L.arima_forecast_batch_device(self.h, d_series, n_series, T, ld, p, d, q,
                                                        int(bool(include_intercept)), d_coef, n_future, d_out, ld_out,
                                                        stream), "arima_forecast_batch_device")
+        if blocking:
+            self.synchronize()
+
+    # ---- the TimeSeriesModel pair: ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects ------------
+    def _effects(self, name, rows, p, d, q, include_intercept, coef, out):
+        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
+        N, T = rows.shape
+        k = p + q + (1 if include_intercept else 0)
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64), (N, k)))
+        if out is None:
+            out = np.empty((N, T))
+        elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.flags.c_contiguous
+                  and out.size == N * T):
+            raise ValueError("out must be a C-contiguous float64 array of the input's size")
+        self._check(getattr(self.L, name)(self.h, _ptr(rows), N, T, p, d, q, int(bool(include_intercept)),
+                                          _ptr(coef), _ptr(out)), name)
+        return out
+
+    def remove_effects(self, series, p, d, q, include_intercept, coef, out=None):
+        """Residuals of every row under its model (ARIMA.scala:629-644); coef (k,) or (N, k). `out` (optional):
+        filled and returned; it may be `series` itself."""
+        return self._effects("arima_remove_effects_batch", series, p, d, q, include_intercept, coef, out)
+
+    def add_effects(self, noise, p, d, q, include_intercept, coef, out=None):
+        """Every row's model driven by the caller's innovations (ARIMA.scala:655-667)."""
+        return self._effects("arima_add_effects_batch", noise, p, d, q, include_intercept, coef, out)
+
+    def remove_effects_device(self, d_series, n_series, T, ld, p, d, q, include_intercept, d_coef, d_out, ld_out,
+                              stream=None, blocking=True):
+        """Device-pointer residuals (ints = raw HBM addresses); d_out may be d_series with ld_out == ld."""
+        self._check(self.L.arima_remove_effects_batch_device(self.h, d_series, n_series, T, ld, p, d, q,
+                                                             int(bool(include_intercept)), d_coef, d_out, ld_out,
+                                                             stream), "arima_remove_effects_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def add_effects_device(self, d_noise, n_series, T, ld, p, d, q, include_intercept, d_coef, d_out, ld_out,
+                           stream=None, blocking=True):
+        """Device-pointer model application; d_out may be d_noise with ld_out == ld."""
+        self._check(self.L.arima_add_effects_batch_device(self.h, d_noise, n_series, T, ld, p, d, q,
+                                                          int(bool(include_intercept)), d_coef, d_out, ld_out,
+                                                          stream), "arima_add_effects_batch_device")
         if blocking:
             self.synchronize()
 

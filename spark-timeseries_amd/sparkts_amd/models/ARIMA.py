@@ -141,8 +141,9 @@ def fit_model(p, d, q, ts, includeIntercept=True, method="css-cgd", userInitPara
 class FitBatchResult:
     """Per-series outputs of a batched fit (the arrays the C ABI fills)."""
 
-    def __init__(self, p, d, q, include_intercept, r, stats):
+    def __init__(self, p, d, q, include_intercept, r, stats, device=None):
         self.p, self.d, self.q, self.has_intercept = p, d, q, include_intercept
+        self._device = device
         self.coefficients = r["coef"]
         self.css_loglik = r["ll"]
         self.status = r["status"]
@@ -159,6 +160,17 @@ class FitBatchResult:
     def converged(self):
         return self.status == _lib.ST_OK
 
+    def residuals(self, series):
+        """removeTimeDependentEffects (ARIMA.scala:629-644) of every series under its own fitted model, one call:
+        (N, T), what lbtest / dwtest / bgtest take. Rows whose status is not OK are NaN."""
+        series = np.ascontiguousarray(np.atleast_2d(series), dtype=np.float64)
+        if series.shape[0] != self.status.shape[0]:
+            raise ValueError("series must hold one row per fitted series")
+        res = _lib.Engine.get(self._device).remove_effects(series, self.p, self.d, self.q, self.has_intercept,
+                                                           self.coefficients)
+        res[self.status != _lib.ST_OK] = np.nan
+        return res
+
 
 def fit_models(p, d, q, series, includeIntercept=True, method="css-cgd", userInitParams=None, device=None):
     """Batched ARIMA.fitModel: `series` is (N, T) float64, one row per series (one Spark partition bucket).
@@ -166,7 +178,7 @@ def fit_models(p, d, q, series, includeIntercept=True, method="css-cgd", userIni
     Never raises for per-series failures; inspect `.status` (ARIMA_ST_* codes, include/sparkts_arima.h)."""
     eng = _lib.Engine.get(device)
     r = eng.fit_batch(series, p, d, q, includeIntercept, _method_code(method), userInitParams)
-    return FitBatchResult(p, d, q, includeIntercept, r, eng.stats())
+    return FitBatchResult(p, d, q, includeIntercept, r, eng.stats(), device=device)
 
 
 def order_search(series, maxp=5, maxd=2, maxq=5, intercept_mode=2, device=None):
@@ -230,6 +242,24 @@ class ARIMAModel:
             eng.sample_device(out.data_ptr(), 1, n, n, self.p, self.d, self.q, self.has_intercept, self.coefficients,
                               0.0, int(seed) & ((1 << 64) - 1), 0)
         return out[0, :n].cpu().numpy()
+
+    def _effects(self, fn, ts, dest_ts):
+        ts = np.asarray(ts, dtype=np.float64).ravel()
+        res = fn(ts[None, :], self.p, self.d, self.q, self.has_intercept, self.coefficients)[0]
+        if dest_ts is None:
+            return res
+        dest_ts[...] = res          # the reference fills destTs and returns it
+        return dest_ts
+
+    def remove_time_dependent_effects(self, ts, dest_ts=None):
+        """removeTimeDependentEffects (ARIMA.scala:629-644; python/sparkts/models/_model.py:7-19): the residuals of
+        `ts` under this model. Returns them; with `dest_ts` given, fills and returns it (it may be `ts`)."""
+        return self._effects(self._eng.remove_effects, ts, dest_ts)
+
+    def add_time_dependent_effects(self, ts, dest_ts=None):
+        """addTimeDependentEffects (ARIMA.scala:655-667; python/sparkts/models/_model.py:21-34): this model driven
+        by the innovations `ts`. Returns the series; with `dest_ts` given, fills and returns it (it may be `ts`)."""
+        return self._effects(self._eng.add_effects, ts, dest_ts)
 
     def forecast(self, ts, nfuture):
         """forecast (ARIMA.scala:696-764)."""

@@ -30,6 +30,29 @@ def fit_arima_partition(records, p, d, q, includeIntercept=True, method="css-cgd
         yield rec if with_status else rec[:2]
 
 
+def arima_residuals_partition(records, p, d, q, includeIntercept=True, method="css-cgd", device=None):
+    """Partition-level drop-in for `mapSeries(v => { val m = ARIMA.fitModel(p, d, q, v);
+    m.removeTimeDependentEffects(v, Vectors.zeros(v.size)) })`: records are bucketed by length, each bucket takes one
+    fit call and one residual call, and the records come back in input order as (key, coefficients, residuals) --
+    what lbtest / dwtest / bgtest (TimeSeriesStatisticalTests.scala:251-320) take. A failed fit yields NaN
+    coefficients and NaN residuals."""
+    records = list(records)
+    keys = [k for k, _ in records]
+    vals = [np.asarray(v, dtype=np.float64).ravel() for _, v in records]
+    out = [None] * len(records)
+    by_len = {}
+    for i, v in enumerate(vals):
+        by_len.setdefault(len(v), []).append(i)
+    for T, idx in by_len.items():
+        batch = np.stack([vals[i] for i in idx]) if T > 0 else np.zeros((len(idx), 0))
+        res = _arima.fit_models(p, d, q, batch, includeIntercept, method, device=device)
+        resid = res.residuals(batch)
+        for j, i in enumerate(idx):
+            out[i] = (keys[i], res.coefficients[j].copy(), resid[j].copy())
+    for rec in out:
+        yield rec
+
+
 def map_series_fit_arima(series_by_key, p, d, q, **kw):
     """Dict/sequence convenience: {key: series} -> {key: coefficients}."""
     items = series_by_key.items() if hasattr(series_by_key, "items") else series_by_key

@@ -1,8 +1,12 @@
 """Measure the SURVEY.md 8(f) rows built this round on one GPU (device-resident inputs):
   forecast      ARIMAModel.forecast (k_forecast) on N x 1024 C2 series, nFuture=30, fitted coefficients
   order_search  C5 grid p,q in [0,5], d in [0,2], +-intercept (216 fits/series) on N x 1024 C2 series
+  effects       (--effects, a run of its own) removeTimeDependentEffects / addTimeDependentEffects (k_effects) on
+                N x 1024 C2 series with fitted (2,1,2)+c coefficients, against the forecast kernel with nFuture = 0 on
+                the same batch: the launches alternate in one process, each timed with HIP events
 Prints one JSON line. Also checks the device-pointer forecast against the host-buffer entry point on 64 rows.
 usage: python tools/bench_next.py [--fc-series N] [--os-series N]
+       python tools/bench_next.py --effects [--fx-series N] [--fx-launches K] [--out FILE]
 """
 import argparse
 import json
@@ -14,12 +18,87 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "spark-timeseries_amd"))
 
 
+def bench_effects(a):
+    """remove / add against forecast(nFuture = 0): the same rows in, the same rows out (16 N T bytes), forecast doing
+    strictly more work per element. Output rows are 128-B aligned (ld = T = 1024)."""
+    import numpy as np
+    import torch
+    import sparkts_amd._lib as L
+    from sparkts_amd import buildinfo
+    eng = L.Engine.get(0)
+    N, T, base = a.fx_series, 1024, [8.2, 0.2, 0.5, 0.3, 0.1]
+    dev = torch.device("cuda:0")
+    s = torch.empty((N, T), dtype=torch.float64, device=dev)
+    eng.sample_device(s.data_ptr(), N, T, T, 2, 1, 2, True, base, 0.05, 20261015)
+    coef = torch.empty((N, 5), dtype=torch.float64, device=dev)
+    ll = torch.empty(N, dtype=torch.float64, device=dev)
+    st = torch.empty(N, dtype=torch.int32, device=dev)
+    eng.fit_batch_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), ll.data_ptr(), st.data_ptr())
+    del ll, st
+    o = torch.empty((N, T), dtype=torch.float64, device=dev)
+    # a stream of the caller's, so that the HIP events bracket the launches (the null stream would select the
+    # handle's own stream, and events recorded on torch's stream would time nothing)
+    ts = torch.cuda.Stream()
+    stream = ts.cuda_stream
+    assert stream, "need a non-default stream"
+    torch.cuda.synchronize()
+    calls = {
+        "forecast": lambda: eng.forecast_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), 0,
+                                                o.data_ptr(), T, stream=stream, blocking=False),
+        "remove": lambda: eng.remove_effects_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(),
+                                                    o.data_ptr(), T, stream=stream, blocking=False),
+        "add": lambda: eng.add_effects_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), o.data_ptr(), T,
+                                              stream=stream, blocking=False),
+    }
+    for _ in range(3):                                       # warm-up: every kernel loaded, clocks up
+        for f in calls.values():
+            f()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in calls}
+    for _ in range(max(a.fx_launches, 20)):                  # alternating launches, one HIP event pair each
+        for k, f in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            f()
+            e1.record(ts)
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {"gpu": torch.cuda.get_device_name(0), "series": N, "T": T, "order": "(2,1,2)+c",
+           "launches_each": len(ev["forecast"]), "bytes_per_launch": 16 * N * T,
+           "library_sha": buildinfo.library_sha(), "source_sha": buildinfo.source_sha()}
+    for k, pairs in ev.items():
+        ms = np.array([e0.elapsed_time(e1) for e0, e1 in pairs])
+        med = float(np.median(ms))
+        out[k] = {"median_ms": med, "min_ms": float(ms.min()), "max_ms": float(ms.max()),
+                  "bytes_per_s": 16.0 * N * T / (med * 1e-3), "series_per_s": N / (med * 1e-3)}
+    bound = out["forecast"]["median_ms"] + (out["forecast"]["max_ms"] - out["forecast"]["min_ms"])
+    out["bound_ms"] = bound                                  # forecast's median + its spread in this run
+    out["remove_within_bound"] = bool(out["remove"]["median_ms"] <= bound)
+    out["add_within_bound"] = bool(out["add"]["median_ms"] <= bound)
+    # the timed kernels computed the host entry point's bits (the last launch was add)
+    host = eng.add_effects(s[:64].cpu().numpy(), 2, 1, 2, True, coef[:64].cpu().numpy())
+    out["device_vs_host_api_identical"] = bool(np.array_equal(host, o[:64].cpu().numpy(), equal_nan=True))
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--effects", action="store_true", help="measure remove / add effects against forecast, only")
+    ap.add_argument("--fx-series", type=int, default=1 << 20)
+    ap.add_argument("--fx-launches", type=int, default=20)
+    ap.add_argument("--out", default=None, help="--effects: also write the JSON line to this file")
     ap.add_argument("--fc-series", type=int, default=1 << 20)
     ap.add_argument("--os-series", type=int, default=1 << 16)
     ap.add_argument("--n-future", type=int, default=30)
     a = ap.parse_args()
+    if a.effects:
+        bench_effects(a)
+        return
     import numpy as np
     import torch
     import sparkts_amd._lib as L
