@@ -149,7 +149,9 @@ int         arima_synchronize(arima_handle *h);
  * runtime order; 2: at every order; 0: always through a k_difference workspace -- identical results),
  * "autofit_slice" (autoFit series per slice of its workspaces, 0 = from free HBM), "host_copy_threads" (host threads
  * that copy arima_fit_batch's rows into pinned blocks for the upload; default 0 = upload from pageable memory through
- * the HIP runtime's staging), "chain_overhead" (k_cg_fit's objective-pass width model; 0 = the kernel's). */
+ * the HIP runtime's staging), "chain_overhead" (k_cg_fit's objective-pass width model; 0 = the kernel's),
+ * "diag_slice_bytes" (residual workspace of one slice of arima_residual_diagnostics_batch*; 0, the default, = 60 % of
+ * the free HBM, at least 1 GiB; results never depend on it). */
 int         arima_set_option(arima_handle *h, const char *name, int64_t value);
 /* Current value of a tuning knob (the names arima_set_option takes); ARIMA_E_INVALID_ARG for an unknown name. */
 int         arima_get_option(const arima_handle *h, const char *name, int64_t *value);
@@ -224,6 +226,38 @@ int arima_remove_effects_batch_device(arima_handle *h, const double *d_series, i
 int arima_add_effects_batch_device(arima_handle *h, const double *d_noise, int64_t n_series, int32_t T,
                                    int64_t ld, int32_t p, int32_t d, int32_t q, int32_t include_intercept,
                                    const double *d_coef, double *d_out, int64_t ld_out, void *stream);
+/* ---- residual diagnostics: autocorr, dwtest, lbtest over a batch ---------------------------------------------- *
+ * Per row of N x T: UnivariateTimeSeries.autocorr(ts, max_lag) (UnivariateTimeSeries.scala:70-96) into acf_out
+ * N x max_lag (lag i at column i - 1), TimeSeriesStatisticalTests.dwtest (TimeSeriesStatisticalTests.scala:251-262)
+ * into dw_out N, and lbtest(ts, max_lag) (:298-307) into lb_stat_out N and lb_pvalue_out N. Every output may be NULL.
+ * acf, dw and the statistic are the reference's arithmetic in its order (nothing special-cased: a constant row or
+ * T - lag == 1 give NaN correlations, NaN and Inf propagate, and the Int product n * (n + 2) of lbtest wraps for
+ * T >= 46340, after which the statistic is negative and the p-value 1). The p-value restates commons-math3's
+ * chi-squared tail and agrees with it to a tolerance, not to bits (csrc/arima_chisq.hpp); where the library would
+ * throw (an infinite statistic) it is NaN.
+ * With any of acf_out, lb_stat_out, lb_pvalue_out requested, max_lag must be in [1, T - 1] (the reference's slicing
+ * and ChiSquaredDistribution(0) throw otherwise): ARIMA_E_INVALID_ARG. With only dw_out, max_lag is ignored.
+ * N == 0 or T == 0 return ARIMA_OK and write nothing. Outputs that overlap the rows or one another return
+ * ARIMA_E_INVALID_ARG. Lags are served 8 at a time: every further 8 cost one more pass pair over the rows.     */
+int arima_diagnostics_batch(arima_handle *h, const double *rows, int64_t n_series, int32_t T, int32_t max_lag,
+                            double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out);
+/* Same, device-resident: d_rows N x T (row stride ld >= T, else ARIMA_E_INVALID_ARG), device outputs */
+int arima_diagnostics_batch_device(arima_handle *h, const double *d_rows, int64_t n_series, int32_t T, int64_t ld,
+                                   int32_t max_lag, double *d_acf_out, double *d_dw_out, double *d_lb_stat_out,
+                                   double *d_lb_pvalue_out, void *stream);
+/* The diagnostics of the residuals of every series under its model, without handing N x T residuals to the caller:
+ * arima_remove_effects_batch into a workspace slice owned by the handle ("diag_slice_bytes"), then the diagnostics
+ * of that slice, slice by slice, so device memory stays bounded whatever N is. Every order the effects entry points
+ * accept; coef N x k. Bit-identical to arima_diagnostics_batch over arima_remove_effects_batch's output.         */
+int arima_residual_diagnostics_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                     int32_t p, int32_t d, int32_t q, int32_t include_intercept, const double *coef,
+                                     int32_t max_lag, double *acf_out, double *dw_out, double *lb_stat_out,
+                                     double *lb_pvalue_out);
+int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                            int64_t ld, int32_t p, int32_t d, int32_t q, int32_t include_intercept,
+                                            const double *d_coef, int32_t max_lag, double *d_acf_out,
+                                            double *d_dw_out, double *d_lb_stat_out, double *d_lb_pvalue_out,
+                                            void *stream);
 /* ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815) for N coefficient rows, flags_out N */
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t n_series, int32_t p, int32_t q,
                             int32_t include_intercept, uint8_t *flags_out);

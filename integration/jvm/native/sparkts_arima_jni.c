@@ -7,8 +7,9 @@
  * (hence `_00024` in the symbol names).
  *
  * Replaces, per call: ARIMA.fitModel over a bucket of equal-length series (ARIMA.scala:79-116),
- * ARIMAModel.forecast (ARIMA.scala:696-764), removeTimeDependentEffects / addTimeDependentEffects (ARIMA.scala:629-667)
- * and the order-search grid (ARIMA.scala:280-375, 826-830).
+ * ARIMAModel.forecast (ARIMA.scala:696-764), removeTimeDependentEffects / addTimeDependentEffects (ARIMA.scala:629-667),
+ * the residual diagnostics autocorr / dwtest / lbtest (UnivariateTimeSeries.scala:70-96,
+ * TimeSeriesStatisticalTests.scala:251-262, :298-307) and the order-search grid (ARIMA.scala:280-375, 826-830).
  */
 #include <jni.h>
 #include <stdint.h>
@@ -81,6 +82,29 @@ JNIEXPORT jint JNICALL JNI_FN(addEffectsBatch)(JNIEnv *env, jobject self, jlong 
     (void)self;
     return arima_add_effects_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, noise), n, t, p, d, q,
                                    intercept ? 1 : 0, (const double *)BUF(env, coef), (double *)BUF(env, out));
+}
+
+/* arima_diagnostics_batch: rows N x T; acf N x maxLag, dw N, lbStat N, lbPvalue N -- any of them may be null */
+JNIEXPORT jint JNICALL JNI_FN(diagnosticsBatch)(JNIEnv *env, jobject self, jlong h, jobject rows, jlong n, jint t,
+                                                jint maxLag, jobject acf, jobject dw, jobject lbStat,
+                                                jobject lbPvalue) {
+    (void)self;
+    return arima_diagnostics_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, rows), n, t, maxLag,
+                                   (double *)BUF(env, acf), (double *)BUF(env, dw), (double *)BUF(env, lbStat),
+                                   (double *)BUF(env, lbPvalue));
+}
+
+/* arima_residual_diagnostics_batch: the same over the residuals of series N x T under the models coef N x k; the
+ * residuals stay on the device */
+JNIEXPORT jint JNICALL JNI_FN(residualDiagnosticsBatch)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n,
+                                                        jint t, jint p, jint d, jint q, jboolean intercept,
+                                                        jobject coef, jint maxLag, jobject acf, jobject dw,
+                                                        jobject lbStat, jobject lbPvalue) {
+    (void)self;
+    return arima_residual_diagnostics_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t, p, d,
+                                            q, intercept ? 1 : 0, (const double *)BUF(env, coef), maxLag,
+                                            (double *)BUF(env, acf), (double *)BUF(env, dw),
+                                            (double *)BUF(env, lbStat), (double *)BUF(env, lbPvalue));
 }
 
 /* arima_order_search_batch: series N x T, order N x 4, coef N x 11, aic N */

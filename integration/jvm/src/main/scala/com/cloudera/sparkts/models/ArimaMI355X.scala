@@ -14,6 +14,11 @@
  *   ArimaMI355X.removeTimeDependentEffectsMany / addTimeDependentEffectsMany
  *                                              batched ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects
  *                                              (ARIMA.scala:629-644, :655-667): residuals and model application
+ *   ArimaMI355X.diagnosticsMany / residualDiagnosticsMany
+ *                                              batched UnivariateTimeSeries.autocorr, dwtest and lbtest
+ *                                              (UnivariateTimeSeries.scala:70-96, TimeSeriesStatisticalTests.scala:251-262,
+ *                                              :298-307) over rows, or over the residuals of series under a model
+ *                                              without bringing the residuals back
  *   ArimaMI355X.autoFit / autoFitMany          drop-in for ARIMA.autoFit (ARIMA.scala:280-375): KPSS choice of d,
  *                                              stepwise walk with the css-bobyqa retry, batched per partition
  *   method = "css-bobyqa"                      fitWithCSSBOBYQA (ARIMA.scala:130-160) on the device
@@ -46,6 +51,11 @@ object ArimaMI355XNative {
                                  intercept: Boolean, coef: DoubleBuffer, out: DoubleBuffer): Int
   @native def addEffectsBatch(handle: Long, noise: DoubleBuffer, n: Long, t: Int, p: Int, d: Int, q: Int,
                               intercept: Boolean, coef: DoubleBuffer, out: DoubleBuffer): Int
+  @native def diagnosticsBatch(handle: Long, rows: DoubleBuffer, n: Long, t: Int, maxLag: Int, acf: DoubleBuffer,
+                               dw: DoubleBuffer, lbStat: DoubleBuffer, lbPvalue: DoubleBuffer): Int
+  @native def residualDiagnosticsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, p: Int, d: Int, q: Int,
+                                       intercept: Boolean, coef: DoubleBuffer, maxLag: Int, acf: DoubleBuffer,
+                                       dw: DoubleBuffer, lbStat: DoubleBuffer, lbPvalue: DoubleBuffer): Int
   @native def orderSearch(handle: Long, series: DoubleBuffer, n: Long, t: Int, maxP: Int, maxD: Int, maxQ: Int,
                           interceptMode: Int, method: Int, order: IntBuffer, coef: DoubleBuffer,
                           aic: DoubleBuffer): Int
@@ -207,6 +217,57 @@ object ArimaMI355X {
   /** Batched ARIMAModel.addTimeDependentEffects (ARIMA.scala:655-667): `model` driven by each row of innovations. */
   def addTimeDependentEffectsMany(model: ARIMAModel, values: Array[Array[Double]]): Array[Array[Double]] =
     effectsMany(model, values, add = true)
+
+  /** Per-series residual diagnostics: autocorr lags 1..maxLag, the Durbin-Watson statistic, and the Ljung-Box
+    * statistic and p-value (lbtest's pair). */
+  case class Diagnostics(acf: Array[Array[Double]], dw: Array[Double], lbStat: Array[Double],
+                         lbPvalue: Array[Double])
+
+  private def diagnosticsOf(n: Int, maxLag: Int)(call: (DoubleBuffer, DoubleBuffer, DoubleBuffer, DoubleBuffer) => Unit)
+      : Diagnostics = {
+    val acf = doubles(math.max(n.toLong * maxLag, 1L))
+    val dw = doubles(math.max(n.toLong, 1L))
+    val stat = doubles(math.max(n.toLong, 1L))
+    val pv = doubles(math.max(n.toLong, 1L))
+    call(acf, dw, stat, pv)
+    Diagnostics(Array.tabulate(n)(i => Array.tabulate(maxLag)(j => acf.get(i * maxLag + j))),
+      Array.tabulate(n)(dw.get), Array.tabulate(n)(stat.get), Array.tabulate(n)(pv.get))
+  }
+
+  /** Batched UnivariateTimeSeries.autocorr(ts, maxLag) (UnivariateTimeSeries.scala:70-96),
+    * TimeSeriesStatisticalTests.dwtest (:251-262) and lbtest(ts, maxLag) (:298-307) of every row; maxLag in
+    * [1, length - 1]. The p-value restates commons-math3's chi-squared tail to a tolerance, not to bits. */
+  def diagnosticsMany(values: Array[Array[Double]], maxLag: Int): Diagnostics = {
+    val n = values.length
+    val t = if (n == 0) 0 else values(0).length
+    require(values.forall(_.length == t), "one call takes series of equal length (bucket by length)")
+    val rows = doubles(math.max(n.toLong * t, 1L))
+    values.foreach(v => rows.put(v))
+    rows.flip()
+    diagnosticsOf(n, maxLag) { (acf, dw, stat, pv) =>
+      check(ArimaMI355XNative.diagnosticsBatch(handle, rows, n, t, maxLag, acf, dw, stat, pv),
+        "arima_diagnostics_batch")
+    }
+  }
+
+  /** The diagnostics of model.removeTimeDependentEffects(v) for every row v, in one call: the residuals are computed
+    * and consumed on the device and never come back. */
+  def residualDiagnosticsMany(model: ARIMAModel, values: Array[Array[Double]], maxLag: Int): Diagnostics = {
+    val n = values.length
+    val t = if (n == 0) 0 else values(0).length
+    require(values.forall(_.length == t), "one call takes series of equal length (bucket by length)")
+    val k = model.coefficients.length
+    val rows = doubles(math.max(n.toLong * t, 1L))
+    values.foreach(v => rows.put(v))
+    rows.flip()
+    val coef = doubles(math.max(n.toLong * k, 1L))
+    (0 until n).foreach(_ => coef.put(model.coefficients))
+    coef.flip()
+    diagnosticsOf(n, maxLag) { (acf, dw, stat, pv) =>
+      check(ArimaMI355XNative.residualDiagnosticsBatch(handle, rows, n, t, model.p, model.d, model.q,
+        model.hasIntercept, coef, maxLag, acf, dw, stat, pv), "arima_residual_diagnostics_batch")
+    }
+  }
 
   /** Drop-in for ARIMA.autoFit (ARIMA.scala:280-304): one series, the reference's exceptions. maxP <= 8 (its
     * css-bobyqa retries have at most 11 parameters). */

@@ -29,6 +29,11 @@ int launch_inverse_difference(const double *in, int64_t ld_in, double *out, int6
 // (arima_effects.hip); out may be exactly in (same stride)
 int launch_effects(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out, int64_t N,
                    int T, int p, int d, int q, int I, int add, hipStream_t s);
+// autocorr lags 1 .. max_lag, dwtest and lbtest (statistic, p-value) of every row (arima_diag.hip); every output is
+// optional. Lags are served kDgW at a time, a pass pair over the rows per group; with only dw_out, max_lag is ignored
+constexpr int kDgW = 8;
+int launch_diag(const double *rows, int64_t ld, int64_t N, int T, int max_lag, double *acf_out, double *dw_out,
+                double *lb_stat_out, double *lb_pvalue_out, hipStream_t s);
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.

@@ -243,6 +243,9 @@ struct arima_handle {
     int search_lanes_used = 0;
     int64_t search_n = 0, search_fits = 0;
     int64_t autofit_slice = 0;     // autoFit series per slice (option "autofit_slice"; 0 = from free HBM)
+    // residual diagnostics (arima_residual_diagnostics_batch*): one slice of residuals, and host-API staging of the outputs
+    int64_t diag_slice_bytes = 0;  // option "diag_slice_bytes"; 0 = 60 % of the free HBM, at least 1 GiB
+    DevBuf dg_resid, dg_acf, dg_dw, dg_lbs, dg_lbp;
 };
 
 namespace {
@@ -625,6 +628,7 @@ int arima_set_option(arima_handle *h, const char *name, int64_t value) {
         return ARIMA_OK;
     }
     if (!strcmp(name, "fit_slice_bytes")) { h->fit_slice_bytes = std::max<int64_t>(0, value); return ARIMA_OK; }
+    if (!strcmp(name, "diag_slice_bytes")) { h->diag_slice_bytes = std::max<int64_t>(0, value); return ARIMA_OK; }
     return set_err(h, ARIMA_E_INVALID_ARG, "unknown option");
 }
 
@@ -639,7 +643,8 @@ int arima_get_option(const arima_handle *hc, const char *name, int64_t *value) {
         {"hr_grid", h->hr_grid}, {"row_pad", h->row_pad}, {"bobyqa_wave", h->bobyqa_wave}, {"merge_live", h->merge_live},
         {"search_express_blocks", h->search_express_blocks}, {"donate_evals", h->donate_evals},
         {"donate_evals_drained", h->donate_evals_drained}, {"fuse_diff", h->fuse_mode}, {"autofit_slice", h->autofit_slice},
-        {"host_copy_threads", h->host_copy_threads}, {"chain_overhead", h->chain_overhead}, {"host_tail", h->host_tail}};
+        {"host_copy_threads", h->host_copy_threads}, {"chain_overhead", h->chain_overhead}, {"host_tail", h->host_tail},
+        {"diag_slice_bytes", h->diag_slice_bytes}};
     for (const auto &o : opts)
         if (!strcmp(name, o.n)) {
             *value = o.v;
@@ -1627,6 +1632,204 @@ int arima_add_effects_batch_device(arima_handle *h, const double *d_noise, int64
                                    int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef, double *d_out,
                                    int64_t ld_out, void *stream) {
     return effects_device(h, d_noise, N, T, ld, p, d, q, I, d_coef, d_out, ld_out, stream, 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// residual diagnostics: autocorr, dwtest, lbtest per row (arima_diag.hip), over given rows or over the residuals of
+// fitted models without handing the N x T residuals to the caller
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct DiagOut {
+    double *acf, *dw, *lbs, *lbp;
+    bool lags() const { return acf || lbs || lbp; }
+    bool any() const { return lags() || dw; }
+};
+
+// shape and lag rules shared by the four entry points; *done: nothing to compute (ARIMA_OK)
+int diag_check(arima_handle *h, int64_t N, int32_t T, int32_t max_lag, const DiagOut &o, bool *done) {
+    *done = false;
+    if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0 || T == 0 || !o.any()) {
+        *done = true;
+        return ARIMA_OK;
+    }
+    // the reference's slicing (UnivariateTimeSeries.scala:75-76) and ChiSquaredDistribution(0) throw
+    if (o.lags() && (max_lag < 1 || max_lag > T - 1)) return set_err(h, ARIMA_E_INVALID_ARG, "max_lag outside [1, T - 1]");
+    return ARIMA_OK;
+}
+
+// no output may meet an input range or another output
+int diag_overlap(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, const void *in0, size_t in0_bytes,
+                 const void *in1, size_t in1_bytes) {
+    const void *ptr[4] = {o.acf, o.dw, o.lbs, o.lbp};
+    const size_t len[4] = {o.acf ? (size_t)N * max_lag * sizeof(double) : 0, o.dw ? (size_t)N * sizeof(double) : 0,
+                           o.lbs ? (size_t)N * sizeof(double) : 0, o.lbp ? (size_t)N * sizeof(double) : 0};
+    for (int a = 0; a < 4; ++a) {
+        if (!ptr[a]) continue;
+        if (::spans_meet(in0, in0_bytes, ptr[a], len[a]) || ::spans_meet(in1, in1_bytes, ptr[a], len[a]))
+            return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
+        for (int b = a + 1; b < 4; ++b)
+            if (ptr[b] && ::spans_meet(ptr[a], len[a], ptr[b], len[b]))
+                return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
+    }
+    return ARIMA_OK;
+}
+
+// device staging of the host entry points' outputs
+int diag_stage(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, DiagOut *dev) {
+    *dev = DiagOut{nullptr, nullptr, nullptr, nullptr};
+    if (o.acf) {
+        RCCHK(h, h->dg_acf.ensure((size_t)N * max_lag * sizeof(double)), "staging");
+        dev->acf = h->dg_acf.as<double>();
+    }
+    if (o.dw) {
+        RCCHK(h, h->dg_dw.ensure((size_t)N * sizeof(double)), "staging");
+        dev->dw = h->dg_dw.as<double>();
+    }
+    if (o.lbs) {
+        RCCHK(h, h->dg_lbs.ensure((size_t)N * sizeof(double)), "staging");
+        dev->lbs = h->dg_lbs.as<double>();
+    }
+    if (o.lbp) {
+        RCCHK(h, h->dg_lbp.ensure((size_t)N * sizeof(double)), "staging");
+        dev->lbp = h->dg_lbp.as<double>();
+    }
+    return ARIMA_OK;
+}
+
+int diag_unstage(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, const DiagOut &dev, hipStream_t s) {
+    if (o.acf) HIPCHK(h, hipMemcpyAsync(o.acf, dev.acf, (size_t)N * max_lag * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (o.dw) HIPCHK(h, hipMemcpyAsync(o.dw, dev.dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (o.lbs) HIPCHK(h, hipMemcpyAsync(o.lbs, dev.lbs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (o.lbp) HIPCHK(h, hipMemcpyAsync(o.lbp, dev.lbp, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+    return ARIMA_OK;
+}
+
+// removeTimeDependentEffects into a bounded workspace slice, then the diagnostics of that slice, slice by slice
+int residual_diag_dev(arima_handle *h, const double *d_series, int64_t N, int T, int64_t ld, int p, int d, int q, int I,
+                      const double *d_coef, int max_lag, const DiagOut &o, hipStream_t s) {
+    const int k = I + p + q;
+    const int64_t ldw = round_up(T, 16);                      // 128-B aligned residual rows
+    int64_t slice_bytes = h->diag_slice_bytes;
+    if (slice_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->dg_resid.bytes) / 10 * 6));
+    }
+    const int64_t slice = std::max<int64_t>(64, slice_bytes / (ldw * (int64_t)sizeof(double)) / 64 * 64);
+    RCCHK(h, h->dg_resid.ensure((size_t)std::min(slice, N) * ldw * sizeof(double)), "residual workspace");
+    double *resid = h->dg_resid.as<double>();
+    for (int64_t f = 0; f < N; f += slice) {
+        const int64_t n = std::min(slice, N - f);
+        RCCHK(h, effects_any(d_series + f * ld, ld, d_coef + f * k, k, resid, ldw, n, T, p, d, q, I, 0, s), "effects");
+        RCCHK(h, sts::launch_diag(resid, ldw, n, T, max_lag, o.acf ? o.acf + f * max_lag : nullptr,
+                                  o.dw ? o.dw + f : nullptr, o.lbs ? o.lbs + f : nullptr,
+                                  o.lbp ? o.lbp + f : nullptr, s), "diagnostics");
+    }
+    return ARIMA_OK;
+}
+}  // namespace
+
+int arima_diagnostics_batch(arima_handle *h, const double *rows, int64_t N, int32_t T, int32_t max_lag,
+                            double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
+    bool done;
+    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
+    if (done) return ARIMA_OK;
+    if (!rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t row_bytes = (size_t)N * T * sizeof(double);
+    RCCHK(h, diag_overlap(h, N, max_lag, o, rows, row_bytes, nullptr, 0), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    DiagOut dev;
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, diag_stage(h, N, max_lag, o, &dev), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, rows, row_bytes, hipMemcpyHostToDevice, s));
+    RCCHK(h, sts::launch_diag(h->h_series.as<double>(), T, N, T, max_lag, dev.acf, dev.dw, dev.lbs, dev.lbp, s),
+          "diagnostics");
+    RCCHK(h, diag_unstage(h, N, max_lag, o, dev, s), "copy");
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+int arima_diagnostics_batch_device(arima_handle *h, const double *d_rows, int64_t N, int32_t T, int64_t ld,
+                                   int32_t max_lag, double *d_acf_out, double *d_dw_out, double *d_lb_stat_out,
+                                   double *d_lb_pvalue_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
+    if (ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    bool done;
+    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
+    if (done) return ARIMA_OK;
+    if (!d_rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    RCCHK(h, diag_overlap(h, N, max_lag, o, d_rows, ((size_t)(N - 1) * ld + T) * sizeof(double), nullptr, 0), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    begin_call(h, s);
+    RCCHK(h, sts::launch_diag(d_rows, ld, N, T, max_lag, o.acf, o.dw, o.lbs, o.lbp, s), "diagnostics");
+    HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
+}
+
+int arima_residual_diagnostics_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
+                                     int32_t d, int32_t q, int32_t I, const double *coef, int32_t max_lag,
+                                     double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
+    if (T < d) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    bool done;
+    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
+    if (done) return ARIMA_OK;
+    const int k = I + p + q;
+    if (!series || (!coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t row_bytes = (size_t)N * T * sizeof(double);
+    RCCHK(h, diag_overlap(h, N, max_lag, o, series, row_bytes, coef, (size_t)N * k * sizeof(double)), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    DiagOut dev;
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
+    RCCHK(h, diag_stage(h, N, max_lag, o, &dev), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
+    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
+    RCCHK(h, residual_diag_dev(h, h->h_series.as<double>(), N, T, T, p, d, q, I, h->h_coef.as<double>(), max_lag, dev, s),
+          "residual diagnostics");
+    RCCHK(h, diag_unstage(h, N, max_lag, o, dev, s), "copy");
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                            int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef,
+                                            int32_t max_lag, double *d_acf_out, double *d_dw_out,
+                                            double *d_lb_stat_out, double *d_lb_pvalue_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
+    if (T < d || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    bool done;
+    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
+    if (done) return ARIMA_OK;
+    const int k = I + p + q;
+    if (!d_series || (!d_coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    RCCHK(h, diag_overlap(h, N, max_lag, o, d_series, ((size_t)(N - 1) * ld + T) * sizeof(double), d_coef,
+                          (size_t)N * k * sizeof(double)), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    begin_call(h, s);
+    RCCHK(h, residual_diag_dev(h, d_series, N, T, ld, p, d, q, I, d_coef, max_lag, o, s), "residual diagnostics");
+    HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
 }
 
 // ---------------------------------------------------------------------------------------------------------

@@ -54,6 +54,8 @@ EXPORTED = [
     "arima_forecast_batch_device", "arima_synchronize", "arima_autofit_batch", "arima_autofit_batch_device",
     "arima_kpss_batch", "arima_remove_effects_batch", "arima_remove_effects_batch_device",
     "arima_add_effects_batch", "arima_add_effects_batch_device",
+    "arima_diagnostics_batch", "arima_diagnostics_batch_device", "arima_residual_diagnostics_batch",
+    "arima_residual_diagnostics_batch_device",
 ]
 
 
@@ -154,6 +156,12 @@ def load():
             fn.argtypes = [H, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _dp, _dp]
         for fn in (L.arima_remove_effects_batch_device, L.arima_add_effects_batch_device):
             fn.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]
+        L.arima_diagnostics_batch.argtypes = [H, _dp, _i64, _i32, _i32, _dp, _dp, _dp, _dp]
+        L.arima_diagnostics_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _vp, _vp, _vp]
+        L.arima_residual_diagnostics_batch.argtypes = [H, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _dp, _i32, _dp, _dp,
+                                                       _dp, _dp]
+        L.arima_residual_diagnostics_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp,
+                                                              _i32, _vp, _vp, _vp, _vp, _vp]
         _lib = L
         return L
 
@@ -365,6 +373,64 @@ class Engine:
         self._check(self.L.arima_add_effects_batch_device(self.h, d_noise, n_series, T, ld, p, d, q,
                                                           int(bool(include_intercept)), d_coef, d_out, ld_out,
                                                           stream), "arima_add_effects_batch_device")
+        if blocking:
+            self.synchronize()
+
+    # ---- residual diagnostics: autocorr, dwtest, lbtest per row ---------------------------------------------
+    DIAG_OUTPUTS = ("acf", "dw", "lb_stat", "lb_pvalue")
+
+    @staticmethod
+    def _diag_bufs(N, max_lag, outputs):
+        unknown = set(outputs) - set(Engine.DIAG_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown diagnostics outputs {sorted(unknown)}")
+        return {name: (np.empty((N, max_lag) if name == "acf" else (N,)) if name in outputs else None)
+                for name in Engine.DIAG_OUTPUTS}
+
+    def diagnostics(self, rows, max_lag, outputs=DIAG_OUTPUTS):
+        """autocorr lags 1..max_lag (N, max_lag), dwtest (N,), lbtest statistic and p-value (N,) of every row
+        (UnivariateTimeSeries.scala:70-96, TimeSeriesStatisticalTests.scala:251-262, :298-307): a dict of the
+        requested `outputs`. With only "dw" requested, max_lag is ignored."""
+        rows = np.ascontiguousarray(np.atleast_2d(rows), dtype=np.float64)
+        N, T = rows.shape
+        o = self._diag_bufs(N, max_lag, outputs)
+        self._check(self.L.arima_diagnostics_batch(self.h, _ptr(rows), N, T, max_lag, _ptr(o["acf"]), _ptr(o["dw"]),
+                                                   _ptr(o["lb_stat"]), _ptr(o["lb_pvalue"])),
+                    "arima_diagnostics_batch")
+        return {k: v for k, v in o.items() if v is not None}
+
+    def residual_diagnostics(self, series, p, d, q, include_intercept, coef, max_lag, outputs=DIAG_OUTPUTS):
+        """`diagnostics` of the residuals of every series under its model (removeTimeDependentEffects,
+        ARIMA.scala:629-644), computed on the device slice by slice: the residuals never reach the host."""
+        series = np.ascontiguousarray(np.atleast_2d(series), dtype=np.float64)
+        N, T = series.shape
+        k = p + q + (1 if include_intercept else 0)
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64), (N, k)))
+        o = self._diag_bufs(N, max_lag, outputs)
+        self._check(self.L.arima_residual_diagnostics_batch(self.h, _ptr(series), N, T, p, d, q,
+                                                            int(bool(include_intercept)), _ptr(coef), max_lag,
+                                                            _ptr(o["acf"]), _ptr(o["dw"]), _ptr(o["lb_stat"]),
+                                                            _ptr(o["lb_pvalue"])),
+                    "arima_residual_diagnostics_batch")
+        return {k_: v for k_, v in o.items() if v is not None}
+
+    def diagnostics_device(self, d_rows, n_series, T, ld, max_lag, d_acf=None, d_dw=None, d_lb_stat=None,
+                           d_lb_pvalue=None, stream=None, blocking=True):
+        """Device-pointer diagnostics (ints = raw HBM addresses; None = output not wanted)."""
+        self._check(self.L.arima_diagnostics_batch_device(self.h, d_rows, n_series, T, ld, max_lag, d_acf, d_dw,
+                                                          d_lb_stat, d_lb_pvalue, stream),
+                    "arima_diagnostics_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def residual_diagnostics_device(self, d_series, n_series, T, ld, p, d, q, include_intercept, d_coef, max_lag,
+                                    d_acf=None, d_dw=None, d_lb_stat=None, d_lb_pvalue=None, stream=None,
+                                    blocking=True):
+        """Device-pointer diagnostics of the residuals under the models in d_coef (N x k)."""
+        self._check(self.L.arima_residual_diagnostics_batch_device(self.h, d_series, n_series, T, ld, p, d, q,
+                                                                   int(bool(include_intercept)), d_coef, max_lag,
+                                                                   d_acf, d_dw, d_lb_stat, d_lb_pvalue, stream),
+                    "arima_residual_diagnostics_batch_device")
         if blocking:
             self.synchronize()
 

@@ -171,6 +171,27 @@ class FitBatchResult:
         res[self.status != _lib.ST_OK] = np.nan
         return res
 
+    def diagnostics(self, series, max_lag):
+        """autocorr(residuals, max_lag), dwtest and lbtest(residuals, max_lag) (UnivariateTimeSeries.scala:70-96,
+        TimeSeriesStatisticalTests.scala:251-262, :298-307) of every series under its own fitted model, one call;
+        the N x T residuals stay on the device. Rows whose status is not OK are NaN."""
+        series = np.ascontiguousarray(np.atleast_2d(series), dtype=np.float64)
+        if series.shape[0] != self.status.shape[0]:
+            raise ValueError("series must hold one row per fitted series")
+        r = _lib.Engine.get(self._device).residual_diagnostics(series, self.p, self.d, self.q, self.has_intercept,
+                                                               self.coefficients, max_lag)
+        for v in r.values():
+            v[self.status != _lib.ST_OK] = np.nan
+        return DiagnosticsResult(max_lag, r)
+
+
+class DiagnosticsResult:
+    """Residual diagnostics of a fitted batch: `acf` (N, max_lag), `dw`, `lb_stat`, `lb_pvalue` (N,)."""
+
+    def __init__(self, max_lag, r):
+        self.max_lag = max_lag
+        self.acf, self.dw, self.lb_stat, self.lb_pvalue = r["acf"], r["dw"], r["lb_stat"], r["lb_pvalue"]
+
 
 def fit_models(p, d, q, series, includeIntercept=True, method="css-cgd", userInitParams=None, device=None):
     """Batched ARIMA.fitModel: `series` is (N, T) float64, one row per series (one Spark partition bucket).

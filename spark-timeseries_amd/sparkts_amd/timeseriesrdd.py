@@ -53,6 +53,29 @@ def arima_residuals_partition(records, p, d, q, includeIntercept=True, method="c
         yield rec
 
 
+def arima_diagnostics_partition(records, p, d, q, max_lag, includeIntercept=True, method="css-cgd", device=None):
+    """Partition-level drop-in for `mapSeries(v => { val m = ARIMA.fitModel(p, d, q, v); val r =
+    m.removeTimeDependentEffects(v, Vectors.zeros(v.size)); (dwtest(r), lbtest(r, maxLag)) })`: records are bucketed by
+    length, each bucket takes one fit call and one diagnostics call (the residuals never leave the device), and the
+    records come back in input order as (key, coefficients, dw, lb_stat, lb_pvalue, acf). A failed fit yields NaNs."""
+    records = list(records)
+    keys = [k for k, _ in records]
+    vals = [np.asarray(v, dtype=np.float64).ravel() for _, v in records]
+    out = [None] * len(records)
+    by_len = {}
+    for i, v in enumerate(vals):
+        by_len.setdefault(len(v), []).append(i)
+    for T, idx in by_len.items():
+        batch = np.stack([vals[i] for i in idx])
+        res = _arima.fit_models(p, d, q, batch, includeIntercept, method, device=device)
+        dg = res.diagnostics(batch, max_lag)
+        for j, i in enumerate(idx):
+            out[i] = (keys[i], res.coefficients[j].copy(), float(dg.dw[j]), float(dg.lb_stat[j]),
+                      float(dg.lb_pvalue[j]), dg.acf[j].copy())
+    for rec in out:
+        yield rec
+
+
 def map_series_fit_arima(series_by_key, p, d, q, **kw):
     """Dict/sequence convenience: {key: series} -> {key: coefficients}."""
     items = series_by_key.items() if hasattr(series_by_key, "items") else series_by_key

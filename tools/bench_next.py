@@ -4,9 +4,14 @@
   effects       (--effects, a run of its own) removeTimeDependentEffects / addTimeDependentEffects (k_effects) on
                 N x 1024 C2 series with fitted (2,1,2)+c coefficients, against the forecast kernel with nFuture = 0 on
                 the same batch: the launches alternate in one process, each timed with HIP events
+  diag          (--diag, a run of its own) the residual diagnostics (k_diag: autocorr, dwtest, lbtest) on the
+                (2,1,2)+c residuals of N x 1024 C2 series: diagnostics_device at max_lag 1, W, W + 1 and 20 and with
+                only dwtest (one pass), residual_diagnostics_device at max_lag W, alternating with
+                remove_effects_device on the same batch in one process, each launch timed with HIP events
 Prints one JSON line. Also checks the device-pointer forecast against the host-buffer entry point on 64 rows.
 usage: python tools/bench_next.py [--fc-series N] [--os-series N]
        python tools/bench_next.py --effects [--fx-series N] [--fx-launches K] [--out FILE]
+       python tools/bench_next.py --diag [--fx-series N] [--fx-launches K] [--out FILE]
 """
 import argparse
 import json
@@ -86,18 +91,102 @@ def bench_effects(a):
     print(line, flush=True)
 
 
+def bench_diag(a):
+    """diagnostics_device with max_lag <= W reads the rows twice (16 N T bytes), remove_effects_device reads and
+    writes them once each (the same bytes): the expectation is the diagnostics median within remove's median plus
+    remove's spread (max - min) in this run. Every further group of W lags is one more pass pair."""
+    import numpy as np
+    import torch
+    import sparkts_amd._lib as L
+    from sparkts_amd import buildinfo
+    eng = L.Engine.get(0)
+    W = 8                                                    # kDgW (csrc/arima_launch.hpp)
+    N, T, base = a.fx_series, 1024, [8.2, 0.2, 0.5, 0.3, 0.1]
+    dev = torch.device("cuda:0")
+    s = torch.empty((N, T), dtype=torch.float64, device=dev)
+    eng.sample_device(s.data_ptr(), N, T, T, 2, 1, 2, True, base, 0.05, 20261015)
+    coef = torch.empty((N, 5), dtype=torch.float64, device=dev)
+    ll = torch.empty(N, dtype=torch.float64, device=dev)
+    st = torch.empty(N, dtype=torch.int32, device=dev)
+    eng.fit_batch_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), ll.data_ptr(), st.data_ptr())
+    del ll, st
+    r = torch.empty((N, T), dtype=torch.float64, device=dev)     # the residuals the diagnostics read
+    o = torch.empty((N, T), dtype=torch.float64, device=dev)     # the timed remove launches write here
+    eng.remove_effects_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), r.data_ptr(), T)
+    acf = torch.empty((N, 20), dtype=torch.float64, device=dev)
+    dw, lbs, lbp = (torch.empty(N, dtype=torch.float64, device=dev) for _ in range(3))
+    ts = torch.cuda.Stream()                                 # see bench_effects
+    stream = ts.cuda_stream
+    assert stream, "need a non-default stream"
+    torch.cuda.synchronize()
+
+    def diag(lag):
+        return lambda: eng.diagnostics_device(r.data_ptr(), N, T, T, lag, acf.data_ptr(), dw.data_ptr(),
+                                              lbs.data_ptr(), lbp.data_ptr(), stream=stream, blocking=False)
+
+    calls = {
+        "remove": lambda: eng.remove_effects_device(s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(),
+                                                    o.data_ptr(), T, stream=stream, blocking=False),
+        "dw_only": lambda: eng.diagnostics_device(r.data_ptr(), N, T, T, 0, None, dw.data_ptr(), None, None,
+                                                  stream=stream, blocking=False),
+        "diag_lag1": diag(1), f"diag_lag{W}": diag(W), f"diag_lag{W + 1}": diag(W + 1), "diag_lag20": diag(20),
+        f"residual_diag_lag{W}": lambda: eng.residual_diagnostics_device(
+            s.data_ptr(), N, T, T, 2, 1, 2, True, coef.data_ptr(), W, acf.data_ptr(), dw.data_ptr(), lbs.data_ptr(),
+            lbp.data_ptr(), stream=stream, blocking=False),
+    }
+    for _ in range(3):                                       # warm-up: every kernel loaded, workspace allocated
+        for f in calls.values():
+            f()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in calls}
+    for _ in range(max(a.fx_launches, 20)):                  # alternating launches, one HIP event pair each
+        for k, f in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            f()
+            e1.record(ts)
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {"gpu": torch.cuda.get_device_name(0), "series": N, "T": T, "order": "(2,1,2)+c", "W": W,
+           "launches_each": len(ev["remove"]), "bytes_per_pass_pair": 16 * N * T,
+           "library_sha": buildinfo.library_sha(), "source_sha": buildinfo.source_sha()}
+    for k, pairs in ev.items():
+        ms = np.array([e0.elapsed_time(e1) for e0, e1 in pairs])
+        out[k] = {"median_ms": float(np.median(ms)), "min_ms": float(ms.min()), "max_ms": float(ms.max())}
+    bound = out["remove"]["median_ms"] + (out["remove"]["max_ms"] - out["remove"]["min_ms"])
+    out["bound_ms"] = bound                                  # remove's median + its spread in this run
+    for k in ("diag_lag1", f"diag_lag{W}"):
+        out[k + "_within_bound"] = bool(out[k]["median_ms"] <= bound)
+    # the last timed launch's outputs equal the host entry point's on the first 64 rows
+    host = eng.residual_diagnostics(s[:64].cpu().numpy(), 2, 1, 2, True, coef[:64].cpu().numpy(), W)
+    out["device_vs_host_api_identical"] = bool(
+        np.array_equal(host["acf"], acf.view(-1)[:64 * W].view(64, W).cpu().numpy(), equal_nan=True)
+        and np.array_equal(host["lb_stat"], lbs[:64].cpu().numpy(), equal_nan=True)
+        and np.array_equal(host["dw"], dw[:64].cpu().numpy(), equal_nan=True))
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--diag", action="store_true", help="measure the residual diagnostics against remove effects, only")
     ap.add_argument("--effects", action="store_true", help="measure remove / add effects against forecast, only")
     ap.add_argument("--fx-series", type=int, default=1 << 20)
     ap.add_argument("--fx-launches", type=int, default=20)
-    ap.add_argument("--out", default=None, help="--effects: also write the JSON line to this file")
+    ap.add_argument("--out", default=None, help="--effects / --diag: also write the JSON line to this file")
     ap.add_argument("--fc-series", type=int, default=1 << 20)
     ap.add_argument("--os-series", type=int, default=1 << 16)
     ap.add_argument("--n-future", type=int, default=30)
     a = ap.parse_args()
     if a.effects:
         bench_effects(a)
+        return
+    if a.diag:
+        bench_diag(a)
         return
     import numpy as np
     import torch
