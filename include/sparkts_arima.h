@@ -299,6 +299,84 @@ int arima_autofit_batch_device(arima_handle *h, const double *d_series, int64_t 
 int arima_kpss_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, double *stat_out,
                      int32_t *status_out);
 
+/* ---- the small model families: EWMA (EWMA.scala) and GARCH(1,1) (GARCH.scala) over a batch --------------------- *
+ * Both fits run commons-math3's Fletcher-Reeves NonLinearConjugateGradientOptimizer with its default LineSearch,
+ * SimpleValueChecker(1e-6, 1e-6), MaxIter(10000), MaxEval(10000), one lane per series (csrc/cg_small.hpp,
+ * csrc/arima_models.hip); results are the reference's arithmetic in its operation order (tests/smallfit_ref.py
+ * restates it). status_out: ARIMA_ST_OK, _MAX_EVAL, _BRACKET_MAX_EVAL, _MAX_ITER or _BAD_INTERVAL (the exceptions the
+ * optimizer can throw); a failed series has NaN parameters and a NaN objective. n_eval_out / n_grad_out (nullable):
+ * the reference's evaluation and gradient counts.
+ *
+ * EWMA.fitModel (EWMA.scala:45-69): one parameter, `smoothing`, from [0.94], GoalType.MINIMIZE of EWMAModel.sse.
+ * GARCH.fitModel (GARCH.scala:33-53): (omega, alpha, beta) from [.2, .2, .2]. No GoalType is passed, so commons
+ *   MAXIMISES GARCHModel.logLikelihood. GARCHModel.gradient returns (alpha, beta, omega) halves (:114) and the
+ *   optimizer applies component 0 to omega, 1 to alpha, 2 to beta: that mismatch is the reference's and is reproduced,
+ *   not repaired -- a drop-in returns what spark-ts returns (on rows far from the start it leaves the positive region).
+ *   Nothing is special-cased: a negative h gives NaN through the log, overflow gives Inf, as Java's doubles do.
+ *
+ * Argument rules (all entry points of this section): fits and the objective / gradient building blocks with T == 0
+ * return ARIMA_E_INVALID_ARG (EWMA reads ts(0)); T >= 1 runs the reference's arithmetic whatever it yields. Effects
+ * with N == 0 or T == 0 return ARIMA_OK and write nothing. ld < T (ld_out < T) returns ARIMA_E_INVALID_ARG. Any
+ * overlap of an output with an input or another output returns ARIMA_E_INVALID_ARG -- there is no in-place form
+ * (EWMA's remove reads ts(i - 1) after arr(i - 1) is written). Nothing is written past column T of a row.
+ * Device variants are asynchronous on the caller's stream and ordered on the handle like every other call.          */
+int arima_ewma_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                         double *smoothing_out, double *sse_out, int32_t *status_out, int32_t *n_eval_out,
+                         int32_t *n_grad_out);
+int arima_ewma_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                double *d_smoothing_out, double *d_sse_out, int32_t *d_status_out,
+                                int32_t *d_n_eval_out, int32_t *d_n_grad_out, void *stream);
+/* coef_out N x 3 = (omega, alpha, beta); ll_out N: logLikelihood at coef_out */
+int arima_garch_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, double *coef_out,
+                          double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out);
+int arima_garch_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                 double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                 int32_t *d_n_grad_out, void *stream);
+/* Building blocks (host buffers): the fit's own pass routine at caller-given parameters, one model per series.
+ * EWMAModel.sse (EWMA.scala:81-96) / gradient (:102-123, the reference's 2 * dJda); smoothing N, out N.
+ * GARCHModel.logLikelihood (GARCH.scala:82-88) / gradient (:96-115); coef N x 3 = (omega, alpha, beta), ll_out N,
+ * grad_out N x 3 in the reference's RETURNED order (alpha, beta, omega). */
+int arima_ewma_sse_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *smoothing,
+                         double *sse_out);
+int arima_ewma_gradient_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                              const double *smoothing, double *grad_out);
+int arima_garch_loglik_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *coef,
+                             double *ll_out);
+int arima_garch_gradient_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *coef,
+                               double *grad_out);
+/* The TimeSeriesModel pairs, N x T in, N x T out, one model per series (smoothing N / coef N x 3).
+ * EWMAModel.removeTimeDependentEffects (EWMA.scala:125-133; reads ts(i - 1), no recursion) and
+ * addTimeDependentEffects (:135-143; the recursion on dest(i - 1)); GARCHModel's (GARCH.scala:131-162). */
+int arima_ewma_remove_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                    const double *smoothing, double *out);
+int arima_ewma_add_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                 const double *smoothing, double *out);
+int arima_garch_remove_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                     const double *coef, double *out);
+int arima_garch_add_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                  const double *coef, double *out);
+int arima_ewma_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                           int64_t ld, const double *d_smoothing, double *d_out, int64_t ld_out,
+                                           void *stream);
+int arima_ewma_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                        int64_t ld, const double *d_smoothing, double *d_out, int64_t ld_out,
+                                        void *stream);
+int arima_garch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                            int64_t ld, const double *d_coef, double *d_out, int64_t ld_out,
+                                            void *stream);
+int arima_garch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                         int64_t ld, const double *d_coef, double *d_out, int64_t ld_out,
+                                         void *stream);
+/* Counters of the last EWMA / GARCH fit call on the handle (waits for its device work). The fit kernel runs one wave
+ * per 64 series in rounds: one joint objective + gradient pass over the wave's rows per round, finished lanes masked. */
+typedef struct arima_model_fit_stats {
+    int64_t n_series;
+    int64_t wave_passes;       /* rounds summed over the waves                                        */
+    int64_t lane_passes;       /* live lanes summed over those rounds (= passes over a series)         */
+    int64_t max_wave_passes;   /* the rounds of the slowest wave                                       */
+} arima_model_fit_stats;
+int arima_get_last_model_fit_stats(arima_handle *h, arima_model_fit_stats *out);
+
 /* ---- synthetic workload generator (ARIMAModel.sample semantics, ARIMA.scala:655-678) ---------------- *
  * Writes N x T series (row stride ld) into device memory: per-series coefficients = base +/- U(0, jitter)
  * (redrawn until stationary and invertible), Philox4x32-10 + Box-Muller N(0,1) noise keyed by (seed,

@@ -127,3 +127,38 @@ JNIEXPORT jint JNICALL JNI_FN(autoFit)(JNIEnv *env, jobject self, jlong h, jobje
                                maxQ, (int32_t *)BUF(env, order), (double *)BUF(env, coef), (double *)BUF(env, aic),
                                (int32_t *)BUF(env, status), (int32_t *)BUF(env, nFits));
 }
+
+/* arima_ewma_fit_batch (EWMA.fitModel, EWMA.scala:45-69): series N x T; smoothing N, sse N, status N, nEval / nGrad N
+ * or null */
+JNIEXPORT jint JNICALL JNI_FN(ewmaFitBatch)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,
+                                            jobject smoothing, jobject sse, jobject status, jobject nEval,
+                                            jobject nGrad) {
+    (void)self;
+    return arima_ewma_fit_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t,
+                                (double *)BUF(env, smoothing), (double *)BUF(env, sse), (int32_t *)BUF(env, status),
+                                (int32_t *)BUF(env, nEval), (int32_t *)BUF(env, nGrad));
+}
+
+/* arima_garch_fit_batch (GARCH.fitModel, GARCH.scala:33-53): series N x T; coef N x 3 (omega, alpha, beta), ll N,
+ * status N, nEval / nGrad N or null */
+JNIEXPORT jint JNICALL JNI_FN(garchFitBatch)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,
+                                             jobject coef, jobject ll, jobject status, jobject nEval, jobject nGrad) {
+    (void)self;
+    return arima_garch_fit_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t,
+                                 (double *)BUF(env, coef), (double *)BUF(env, ll), (int32_t *)BUF(env, status),
+                                 (int32_t *)BUF(env, nEval), (int32_t *)BUF(env, nGrad));
+}
+
+/* The TimeSeriesModel pairs of EWMAModel (EWMA.scala:125-143; smoothing N) and GARCHModel (GARCH.scala:131-162;
+ * coef N x 3): series N x T, out N x T (out may not overlap an input) */
+#define MODEL_EFFECTS_FN(jname, cname)                                                                             \
+    JNIEXPORT jint JNICALL JNI_FN(jname)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,      \
+                                         jobject params, jobject out) {                                            \
+        (void)self;                                                                                                \
+        return cname((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t,                          \
+                     (const double *)BUF(env, params), (double *)BUF(env, out));                                   \
+    }
+MODEL_EFFECTS_FN(ewmaRemoveEffectsBatch, arima_ewma_remove_effects_batch)
+MODEL_EFFECTS_FN(ewmaAddEffectsBatch, arima_ewma_add_effects_batch)
+MODEL_EFFECTS_FN(garchRemoveEffectsBatch, arima_garch_remove_effects_batch)
+MODEL_EFFECTS_FN(garchAddEffectsBatch, arima_garch_add_effects_batch)

@@ -62,6 +62,19 @@ object ArimaMI355XNative {
   @native def autoFit(handle: Long, series: DoubleBuffer, n: Long, t: Int, maxP: Int, maxD: Int, maxQ: Int,
                       order: IntBuffer, coef: DoubleBuffer, aic: DoubleBuffer, status: IntBuffer,
                       nFits: IntBuffer): Int
+  // the small models (EWMA.scala, GARCH.scala): one model per series; smoothing N, coef N x 3 = (omega, alpha, beta)
+  @native def ewmaFitBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, smoothing: DoubleBuffer,
+                           sse: DoubleBuffer, status: IntBuffer, nEval: IntBuffer, nGrad: IntBuffer): Int
+  @native def garchFitBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                            ll: DoubleBuffer, status: IntBuffer, nEval: IntBuffer, nGrad: IntBuffer): Int
+  @native def ewmaRemoveEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, smoothing: DoubleBuffer,
+                                     out: DoubleBuffer): Int
+  @native def ewmaAddEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, smoothing: DoubleBuffer,
+                                  out: DoubleBuffer): Int
+  @native def garchRemoveEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                                      out: DoubleBuffer): Int
+  @native def garchAddEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                                   out: DoubleBuffer): Int
 }
 
 /** Per-series status codes of include/sparkts_arima.h, mapped back to the exception the reference throws. */
@@ -317,4 +330,93 @@ object ArimaMI355X {
     (Array.tabulate(n)(i => Array.tabulate(4)(j => order.get(4 * i + j))),
       Array.tabulate(n)(i => Array.tabulate(11)(j => coef.get(11 * i + j))), Array.tabulate(n)(aic.get))
   }
+
+  // ---- the small models: EWMA (EWMA.scala) and GARCH(1,1) (GARCH.scala) ------------------------------------------
+  /** Result of a batched EWMA / GARCH fit: K parameters per series (EWMA: smoothing; GARCH: omega, alpha, beta), the
+    * objective there (sse / logLikelihood), the status and the reference's evaluation counters. */
+  case class ModelFitResult(params: Array[Array[Double]], objective: Array[Double], status: Array[Int],
+                            nEval: Array[Int], nGrad: Array[Int])
+
+  private def packRows(values: Array[Array[Double]]): (DoubleBuffer, Int, Int) = {
+    val n = values.length
+    val t = if (n == 0) 0 else values(0).length
+    require(values.forall(_.length == t), "one call takes series of equal length (bucket by length)")
+    val rows = doubles(math.max(n.toLong * t, 1L))
+    values.foreach(v => rows.put(v))
+    rows.flip()
+    (rows, n, t)
+  }
+
+  private def modelFitMany(values: Array[Array[Double]], k: Int, what: String)(
+      call: (DoubleBuffer, Int, Int, DoubleBuffer, DoubleBuffer, IntBuffer, IntBuffer, IntBuffer) => Int)
+      : ModelFitResult = {
+    val (rows, n, t) = packRows(values)
+    val par = doubles(math.max(n.toLong * k, 1L))
+    val obj = doubles(math.max(n, 1))
+    val status = ints(math.max(n, 1))
+    val nEval = ints(math.max(n, 1))
+    val nGrad = ints(math.max(n, 1))
+    check(call(rows, n, t, par, obj, status, nEval, nGrad), what)
+    ModelFitResult(Array.tabulate(n)(i => Array.tabulate(k)(j => par.get(i * k + j))), Array.tabulate(n)(obj.get),
+      Array.tabulate(n)(status.get), Array.tabulate(n)(nEval.get), Array.tabulate(n)(nGrad.get))
+  }
+
+  /** One ABI call (arima_ewma_fit_batch) for a bucket of equal-length series: EWMA.fitModel of every row. */
+  def ewmaFitMany(values: Array[Array[Double]]): ModelFitResult =
+    modelFitMany(values, 1, "arima_ewma_fit_batch") { (rows, n, t, par, obj, st, ne, ng) =>
+      ArimaMI355XNative.ewmaFitBatch(handle, rows, n, t, par, obj, st, ne, ng)
+    }
+
+  /** One ABI call (arima_garch_fit_batch): GARCH.fitModel of every row, with the reference's gradient order. */
+  def garchFitMany(values: Array[Array[Double]]): ModelFitResult =
+    modelFitMany(values, 3, "arima_garch_fit_batch") { (rows, n, t, par, obj, st, ne, ng) =>
+      ArimaMI355XNative.garchFitBatch(handle, rows, n, t, par, obj, st, ne, ng)
+    }
+
+  /** Drop-in for EWMA.fitModel (EWMA.scala:45-69): a batch of one, the optimizer's exceptions. */
+  def ewmaFitModel(ts: Vector): EWMAModel = {
+    val r = ewmaFitMany(Array(ts.toArray))
+    if (r.status(0) != ArimaStatus.OK) throw ArimaStatus.toException(r.status(0))
+    new EWMAModel(r.params(0)(0))
+  }
+
+  /** Drop-in for GARCH.fitModel (GARCH.scala:33-53). */
+  def garchFitModel(ts: Vector): GARCHModel = {
+    val r = garchFitMany(Array(ts.toArray))
+    if (r.status(0) != ArimaStatus.OK) throw ArimaStatus.toException(r.status(0))
+    new GARCHModel(r.params(0)(0), r.params(0)(1), r.params(0)(2))
+  }
+
+  private def modelEffectsMany(values: Array[Array[Double]], params: Array[Double], what: String)(
+      call: (DoubleBuffer, Int, Int, DoubleBuffer, DoubleBuffer) => Int): Array[Array[Double]] = {
+    val (rows, n, t) = packRows(values)
+    val par = doubles(math.max(n.toLong * params.length, 1L))
+    (0 until n).foreach(_ => par.put(params))
+    par.flip()
+    val out = doubles(math.max(n.toLong * t, 1L))
+    check(call(rows, n, t, par, out), what)
+    Array.tabulate(n)(i => Array.tabulate(t)(j => out.get(i * t + j)))
+  }
+
+  /** Batched EWMAModel.removeTimeDependentEffects / addTimeDependentEffects (EWMA.scala:125-143). */
+  def removeTimeDependentEffectsMany(model: EWMAModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, Array(model.smoothing), "arima_ewma_remove_effects_batch") { (rows, n, t, par, out) =>
+      ArimaMI355XNative.ewmaRemoveEffectsBatch(handle, rows, n, t, par, out)
+    }
+
+  def addTimeDependentEffectsMany(model: EWMAModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, Array(model.smoothing), "arima_ewma_add_effects_batch") { (rows, n, t, par, out) =>
+      ArimaMI355XNative.ewmaAddEffectsBatch(handle, rows, n, t, par, out)
+    }
+
+  /** Batched GARCHModel.removeTimeDependentEffects / addTimeDependentEffects (GARCH.scala:131-162). */
+  def removeTimeDependentEffectsMany(model: GARCHModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, Array(model.omega, model.alpha, model.beta), "arima_garch_remove_effects_batch") {
+      (rows, n, t, par, out) => ArimaMI355XNative.garchRemoveEffectsBatch(handle, rows, n, t, par, out)
+    }
+
+  def addTimeDependentEffectsMany(model: GARCHModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, Array(model.omega, model.alpha, model.beta), "arima_garch_add_effects_batch") {
+      (rows, n, t, par, out) => ArimaMI355XNative.garchAddEffectsBatch(handle, rows, n, t, par, out)
+    }
 }

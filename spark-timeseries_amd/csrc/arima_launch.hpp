@@ -34,6 +34,21 @@ int launch_effects(const double *in, int64_t ld_in, const double *coef, int k, d
 constexpr int kDgW = 8;
 int launch_diag(const double *rows, int64_t ld, int64_t N, int T, int max_lag, double *acf_out, double *dw_out,
                 double *lb_stat_out, double *lb_pvalue_out, hipStream_t s);
+// ---- the small models: EWMA and GARCH(1,1) (arima_models.hip; cg_small.hpp, model_pass.hpp) ----
+// params / coef_out hold K doubles per series: EWMA (smoothing), GARCH (omega, alpha, beta)
+constexpr int kModelEwma = 0, kModelGarch = 1;
+inline int model_num_params(int model) { return model == kModelEwma ? 1 : 3; }
+constexpr int kModelCtlWords = 3;  // k_model_fit's counters: wave passes, live lane-passes, the largest pass count of a wave
+// EWMA.fitModel / GARCH.fitModel of every row (T >= 1); n_eval_out, n_grad_out and ctl are optional
+int launch_model_fit(int model, const double *rows, int64_t ld, int64_t N, int T, double *coef_out, double *obj_out,
+                     int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, unsigned long long *ctl,
+                     hipStream_t s);
+// objective (f_out N) and gradient (g_out N x K, the reference's returned order) at params; either output optional
+int launch_model_eval(int model, const double *rows, int64_t ld, int64_t N, int T, const double *params, double *f_out,
+                      double *g_out, hipStream_t s);
+// removeTimeDependentEffects (add == 0) / addTimeDependentEffects (add == 1); out may not overlap in
+int launch_model_effects(int model, const double *in, int64_t ld_in, const double *params, double *out, int64_t ld_out,
+                         int64_t N, int T, int add, hipStream_t s);
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.

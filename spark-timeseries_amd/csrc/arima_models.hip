@@ -1,0 +1,252 @@
+// arima_models.hip — the small model families of spark-ts over a batch, one lane per series:
+//   EWMA        EWMA.fitModel (EWMA.scala:45-69), EWMAModel.sse / gradient and its TimeSeriesModel pair (:81-143)
+//   GARCH(1,1)  GARCH.fitModel (GARCH.scala:33-53), GARCHModel.logLikelihood / gradient and its pair (:82-162)
+// Both fits run commons-math3's Fletcher-Reeves NonLinearConjugateGradientOptimizer with its default LineSearch under
+// SimpleValueChecker(1e-6, 1e-6), MaxIter(10000), MaxEval(10000): cg_small.hpp restates it as a per-series state machine
+// (EWMA minimises sse; GARCH passes no GoalType, so commons maximises the log-likelihood). The objectives and the pairs
+// are the one-pass recursions of model_pass.hpp, the reference's operations in its order; tests/smallfit_ref.py is the
+// CPU restatement the results equal bit for bit.
+//
+// The reference's gradient-order quirk is reproduced, not repaired: GARCHModel.gradient returns (alpha, beta, omega)
+// halves while the optimizer's parameters are (omega, alpha, beta), so omega moves along alpha's derivative, alpha along
+// beta's and beta along omega's. A drop-in returns what spark-ts returns.
+//
+// k_model_fit<Model>: one wave per 64 series, wave-synchronous rounds. Every live lane has one posted point; one joint
+// pass over the wave's rows computes objective and gradient at each lane's point; each lane advances its machine;
+// finished lanes are masked; the wave leaves when all are done. Rows stream through k_effects' coalesced
+// [64 series x 32 steps] LDS tiles (arima_effects.hip), the next tile prefetched into registers while this one is
+// consumed; rows of finished lanes and rows past N are not read (their tile entries are never consumed). Everything
+// carried across tile boundaries is in registers (Model::Pass). No stragglers are moved and no row stays resident:
+// the counters (wave passes, live lane-passes, the largest pass count of a wave) are there to decide that from numbers.
+// k_model_eval<Model>: objective and gradient at caller-given parameters, the same pass routine as the fit's.
+// k_model_effects<Model, ADD>: one streaming pass, N x T in, N x T out, independent strides.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/sparkts_arima.h"
+#include "arima_launch.hpp"
+#include "model_pass.hpp"
+
+namespace sts {
+
+using namespace sts::small;
+
+constexpr int kMdWave = 64;
+constexpr int kMdCh = 32;                         // time steps per tile
+constexpr int kMdRowsPerLd = kMdWave / kMdCh;     // rows per coalesced load instruction
+static_assert(kMdWave % kMdCh == 0, "tile width must divide the wave");
+
+typedef double MdTile[kMdWave][kMdCh + 1];
+
+// One tile of rows into registers: lane reads element tu of row j * kMdRowsPerLd + tr for the rows in `rows_mask`
+// (bit r = row row0 + r is wanted; bits of rows >= N are never set). The column is clamped, so no load leaves the row.
+__device__ __forceinline__ void md_load_tile(double (&pf)[kMdCh], const double *__restrict__ in, int64_t ld,
+                                             int64_t row0, int T, int cb, int lane, unsigned long long rows_mask) {
+    const int tu = lane % kMdCh, tr = lane / kMdCh;
+    const int t = cb + tu < T ? cb + tu : T - 1;
+#pragma unroll
+    for (int j = 0; j < kMdCh; ++j) {
+        const int r = j * kMdRowsPerLd + tr;
+        pf[j] = ((rows_mask >> r) & 1ull) ? in[(row0 + r) * ld + t] : 0.0;
+    }
+}
+
+__device__ __forceinline__ void md_store_tile(MdTile &tile, const double (&pf)[kMdCh], int lane) {
+    const int tu = lane % kMdCh, tr = lane / kMdCh;
+#pragma unroll
+    for (int j = 0; j < kMdCh; ++j) tile[j * kMdRowsPerLd + tr][tu] = pf[j];
+}
+
+// The joint pass of one round: objective f and gradient g at each live lane's point x
+template <class Model>
+__device__ __forceinline__ void md_wave_pass(MdTile &tile, const double *__restrict__ rows, int64_t ld, int64_t row0,
+                                             int T, int lane, unsigned long long live_mask, bool live, const double *x,
+                                             double *f, double *g) {
+    typename Model::Pass ps;
+    ps.begin(x);
+    double pf[kMdCh];
+    md_load_tile(pf, rows, ld, row0, T, 0, lane, live_mask);
+    for (int cb = 0; cb < T; cb += kMdCh) {
+        __syncthreads();                                               // the last tile has been consumed
+        md_store_tile(tile, pf, lane);
+        __syncthreads();
+        if (cb + kMdCh < T) md_load_tile(pf, rows, ld, row0, T, cb + kMdCh, lane, live_mask);
+        const int ce = cb + kMdCh < T ? cb + kMdCh : T;
+        if (live) {
+#pragma unroll 1
+            for (int t = cb; t < ce; ++t) ps.step(t, tile[lane][t - cb]);
+        }
+    }
+    ps.end(T, f, g);
+}
+
+// ctl: [0] wave passes, [1] live lane-passes, [2] the largest pass count of a wave (nullable)
+template <class Model>
+__global__ __launch_bounds__(kMdWave) void k_model_fit(const double *__restrict__ rows, int64_t ld, int64_t N, int T,
+                                                       double *__restrict__ coef_out, double *__restrict__ obj_out,
+                                                       int32_t *__restrict__ status_out,
+                                                       int32_t *__restrict__ n_eval_out,
+                                                       int32_t *__restrict__ n_grad_out, unsigned long long *ctl) {
+    constexpr int K = Model::K;
+    __shared__ MdTile tile;
+    const int lane = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
+    const int64_t sid = row0 + lane;
+    SmallCG<K, Model::kMinimize> m;
+    {
+        double x0[K];
+        Model::initial_guess(x0);
+        m.start(x0, 1e-6);                                             // new SimpleValueChecker(1e-6, 1e-6)
+    }
+    if (sid >= N) m.pc = SmallCG<K, Model::kMinimize>::DONE;          // lanes past N never post a point
+    unsigned long long passes = 0, lane_passes = 0;
+    for (;;) {
+        const bool live = !m.done();
+        const unsigned long long live_mask = __ballot(live);
+        if (live_mask == 0) break;
+        double f, g[K];
+        md_wave_pass<Model>(tile, rows, ld, row0, T, lane, live_mask, live, m.xreq(), &f, g);
+        if (live) m.advance(f, g);
+        ++passes;
+        lane_passes += (unsigned long long)__popcll(live_mask);
+    }
+    if (sid < N) {
+        double coef[K], obj;
+        m.result(coef, &obj);
+#pragma unroll
+        for (int j = 0; j < K; ++j) coef_out[sid * K + j] = coef[j];
+        obj_out[sid] = obj;
+        status_out[sid] = m.status;
+        if (n_eval_out) n_eval_out[sid] = m.n_eval;
+        if (n_grad_out) n_grad_out[sid] = m.n_grad;
+    }
+    if (ctl && lane == 0) {
+        atomicAdd(&ctl[0], passes);
+        atomicAdd(&ctl[1], lane_passes);
+        atomicMax(&ctl[2], passes);
+    }
+}
+
+template <class Model>
+__global__ __launch_bounds__(kMdWave) void k_model_eval(const double *__restrict__ rows, int64_t ld, int64_t N, int T,
+                                                        const double *__restrict__ params, double *__restrict__ f_out,
+                                                        double *__restrict__ g_out) {
+    constexpr int K = Model::K;
+    __shared__ MdTile tile;
+    const int lane = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
+    const int64_t sid = row0 + lane;
+    const bool live = sid < N;
+    double x[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) x[j] = live ? params[sid * K + j] : 0.0;
+    double f, g[K];
+    md_wave_pass<Model>(tile, rows, ld, row0, T, lane, __ballot(live), live, x, &f, g);
+    if (live) {
+        if (f_out) f_out[sid] = f;
+        if (g_out) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) g_out[sid * K + j] = g[j];
+        }
+    }
+}
+
+// in_all and out_all are distinct ranges (the entry points refuse any overlap)
+template <class Model, bool ADD>
+__global__ __launch_bounds__(kMdWave) void k_model_effects(const double *__restrict__ in_all, int64_t ld_in,
+                                                           const double *__restrict__ params,
+                                                           double *__restrict__ out_all, int64_t ld_out, int64_t N,
+                                                           int T) {
+    constexpr int K = Model::K;
+    __shared__ MdTile tile;
+    const int lane = (int)threadIdx.x;
+    const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
+    const int64_t sid = row0 + lane;
+    const bool live = sid < N;
+    const unsigned long long live_mask = __ballot(live);
+    double x[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) x[j] = live ? params[sid * K + j] : 0.0;
+    typename Model::template Fx<ADD> fx;
+    fx.begin(x);
+    const int tu = lane % kMdCh, tr = lane / kMdCh;
+    double pf[kMdCh];
+    md_load_tile(pf, in_all, ld_in, row0, T, 0, lane, live_mask);
+    for (int cb = 0; cb < T; cb += kMdCh) {
+        __syncthreads();                                               // last tile's flush has read the LDS
+        md_store_tile(tile, pf, lane);
+        __syncthreads();
+        if (cb + kMdCh < T) md_load_tile(pf, in_all, ld_in, row0, T, cb + kMdCh, lane, live_mask);
+        const int ce = cb + kMdCh < T ? cb + kMdCh : T;
+        if (live) {
+#pragma unroll 1
+            for (int t = cb; t < ce; ++t) tile[lane][t - cb] = fx.step(t, tile[lane][t - cb]);
+        }
+        __syncthreads();                                               // tile entries of every lane written
+        const int idx = cb + tu;
+        if (idx < T) {
+#pragma unroll
+            for (int j = 0; j < kMdCh; ++j) {
+                const int r = j * kMdRowsPerLd + tr;
+                if (row0 + r < N) out_all[(row0 + r) * ld_out + idx] = tile[r][tu];
+            }
+        }
+    }
+}
+
+static inline dim3 md_grid(int64_t N) { return dim3((unsigned)((N + kMdWave - 1) / kMdWave)); }
+
+int launch_model_fit(int model, const double *rows, int64_t ld, int64_t N, int T, double *coef_out, double *obj_out,
+                     int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, unsigned long long *ctl,
+                     hipStream_t s) {
+    if (N == 0) return ARIMA_OK;
+    if (T < 1 || ld < T) return ARIMA_E_INVALID_ARG;
+    if (model == kModelEwma)
+        hipLaunchKernelGGL((k_model_fit<Ewma>), md_grid(N), dim3(kMdWave), 0, s, rows, ld, N, T, coef_out, obj_out,
+                           status_out, n_eval_out, n_grad_out, ctl);
+    else if (model == kModelGarch)
+        hipLaunchKernelGGL((k_model_fit<Garch>), md_grid(N), dim3(kMdWave), 0, s, rows, ld, N, T, coef_out, obj_out,
+                           status_out, n_eval_out, n_grad_out, ctl);
+    else
+        return ARIMA_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return ARIMA_E_DEVICE;
+    return ARIMA_OK;
+}
+
+int launch_model_eval(int model, const double *rows, int64_t ld, int64_t N, int T, const double *params, double *f_out,
+                      double *g_out, hipStream_t s) {
+    if (N == 0) return ARIMA_OK;
+    if (T < 1 || ld < T) return ARIMA_E_INVALID_ARG;
+    if (model == kModelEwma)
+        hipLaunchKernelGGL((k_model_eval<Ewma>), md_grid(N), dim3(kMdWave), 0, s, rows, ld, N, T, params, f_out, g_out);
+    else if (model == kModelGarch)
+        hipLaunchKernelGGL((k_model_eval<Garch>), md_grid(N), dim3(kMdWave), 0, s, rows, ld, N, T, params, f_out, g_out);
+    else
+        return ARIMA_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return ARIMA_E_DEVICE;
+    return ARIMA_OK;
+}
+
+template <class Model>
+static void launch_model_effects_dir(const double *in, int64_t ld_in, const double *params, double *out, int64_t ld_out,
+                                     int64_t N, int T, int add, hipStream_t s) {
+    if (add)
+        hipLaunchKernelGGL((k_model_effects<Model, true>), md_grid(N), dim3(kMdWave), 0, s, in, ld_in, params, out,
+                           ld_out, N, T);
+    else
+        hipLaunchKernelGGL((k_model_effects<Model, false>), md_grid(N), dim3(kMdWave), 0, s, in, ld_in, params, out,
+                           ld_out, N, T);
+}
+
+int launch_model_effects(int model, const double *in, int64_t ld_in, const double *params, double *out, int64_t ld_out,
+                         int64_t N, int T, int add, hipStream_t s) {
+    if (N == 0 || T == 0) return ARIMA_OK;
+    if (T < 0 || ld_in < T || ld_out < T) return ARIMA_E_INVALID_ARG;
+    if (model == kModelEwma) launch_model_effects_dir<Ewma>(in, ld_in, params, out, ld_out, N, T, add, s);
+    else if (model == kModelGarch) launch_model_effects_dir<Garch>(in, ld_in, params, out, ld_out, N, T, add, s);
+    else return ARIMA_E_UNSUPPORTED;
+    if (hipGetLastError() != hipSuccess) return ARIMA_E_DEVICE;
+    return ARIMA_OK;
+}
+
+}  // namespace sts

@@ -246,6 +246,9 @@ struct arima_handle {
     // residual diagnostics (arima_residual_diagnostics_batch*): one slice of residuals, and host-API staging of the outputs
     int64_t diag_slice_bytes = 0;  // option "diag_slice_bytes"; 0 = 60 % of the free HBM, at least 1 GiB
     DevBuf dg_resid, dg_acf, dg_dw, dg_lbs, dg_lbp;
+    // the small models (EWMA, GARCH): the fit kernel's counters of the last fit, and host-API staging of N x T outputs
+    DevBuf md_ctl, md_out;
+    int64_t md_last_n = -1;        // series of the last EWMA / GARCH fit (-1: none yet)
 };
 
 namespace {
@@ -2371,6 +2374,276 @@ int arima_sample_batch_device(arima_handle *h, double *d_series, int64_t N, int3
     begin_call(h, s);
     RCCHK(h, sts::launch_sample(d_series, ld, N, T, p, d, q, I, base_coef, jitter, seed, first_series, s), "sample");
     HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// the small models: EWMA and GARCH(1,1) (arima_models.hip) -- fits, objective / gradient, the TimeSeriesModel pairs
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct Span {
+    const void *p;
+    size_t bytes;
+};
+
+// no output may meet an input or another output
+int md_overlap(arima_handle *h, const Span *in, int n_in, const Span *out, int n_out) {
+    for (int a = 0; a < n_out; ++a) {
+        if (!out[a].p) continue;
+        for (int b = 0; b < n_in; ++b)
+            if (in[b].p && ::spans_meet(in[b].p, in[b].bytes, out[a].p, out[a].bytes))
+                return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
+        for (int b = a + 1; b < n_out; ++b)
+            if (out[b].p && ::spans_meet(out[a].p, out[a].bytes, out[b].p, out[b].bytes))
+                return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
+    }
+    return ARIMA_OK;
+}
+
+int md_fit_launch(arima_handle *h, int model, const double *rows, int64_t ld, int64_t N, int T, double *coef,
+                  double *obj, int32_t *status, int32_t *n_eval, int32_t *n_grad, hipStream_t s) {
+    RCCHK(h, h->md_ctl.ensure(sts::kModelCtlWords * sizeof(unsigned long long)), "counters");
+    HIPCHK(h, hipMemsetAsync(h->md_ctl.ptr, 0, sts::kModelCtlWords * sizeof(unsigned long long), s));
+    RCCHK(h, sts::launch_model_fit(model, rows, ld, N, T, coef, obj, status, n_eval, n_grad,
+                                   h->md_ctl.as<unsigned long long>(), s), "model fit");
+    h->md_last_n = N;
+    return ARIMA_OK;
+}
+
+int md_fit_host(arima_handle *h, int model, const double *series, int64_t N, int32_t T, double *coef_out,
+                double *obj_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0) return ARIMA_OK;
+    if (!series || !coef_out || !obj_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int K = sts::model_num_params(model);
+    const size_t row_bytes = (size_t)N * T * sizeof(double), nd = (size_t)N * sizeof(double),
+                 ni = (size_t)N * sizeof(int32_t);
+    const Span in[1] = {{series, row_bytes}};
+    const Span out[5] = {{coef_out, nd * K}, {obj_out, nd}, {status_out, ni}, {n_eval_out, ni}, {n_grad_out, ni}};
+    RCCHK(h, md_overlap(h, in, 1, out, 5), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, h->h_coef.ensure(nd * K), "staging");
+    RCCHK(h, h->h_ll.ensure(nd), "staging");
+    RCCHK(h, h->h_status.ensure(ni), "staging");
+    RCCHK(h, h->h_neval.ensure(ni), "staging");
+    RCCHK(h, h->h_ngrad.ensure(ni), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
+    RCCHK(h, md_fit_launch(h, model, h->h_series.as<double>(), T, N, T, h->h_coef.as<double>(), h->h_ll.as<double>(),
+                           h->h_status.as<int32_t>(), h->h_neval.as<int32_t>(), h->h_ngrad.as<int32_t>(), s), "fit");
+    HIPCHK(h, hipMemcpyAsync(coef_out, h->h_coef.ptr, nd * K, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(obj_out, h->h_ll.ptr, nd, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(status_out, h->h_status.ptr, ni, hipMemcpyDeviceToHost, s));
+    if (n_eval_out) HIPCHK(h, hipMemcpyAsync(n_eval_out, h->h_neval.ptr, ni, hipMemcpyDeviceToHost, s));
+    if (n_grad_out) HIPCHK(h, hipMemcpyAsync(n_grad_out, h->h_ngrad.ptr, ni, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+int md_fit_device(arima_handle *h, int model, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                  double *d_coef_out, double *d_obj_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                  int32_t *d_n_grad_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (N < 0 || T < 1 || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0) return ARIMA_OK;
+    if (!d_series || !d_coef_out || !d_obj_out || !d_status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int K = sts::model_num_params(model);
+    const size_t nd = (size_t)N * sizeof(double), ni = (size_t)N * sizeof(int32_t);
+    const Span in[1] = {{d_series, ((size_t)(N - 1) * ld + T) * sizeof(double)}};
+    const Span out[5] = {{d_coef_out, nd * K}, {d_obj_out, nd}, {d_status_out, ni}, {d_n_eval_out, ni},
+                         {d_n_grad_out, ni}};
+    RCCHK(h, md_overlap(h, in, 1, out, 5), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    begin_call(h, s);
+    RCCHK(h, md_fit_launch(h, model, d_series, ld, N, T, d_coef_out, d_obj_out, d_status_out, d_n_eval_out,
+                           d_n_grad_out, s), "fit");
+    HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
+}
+
+// objective (want_grad == 0: out N) or gradient (out N x K) at params (N x K), host buffers
+int md_eval_host(arima_handle *h, int model, const double *series, int64_t N, int32_t T, const double *params,
+                 double *out, int want_grad) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0) return ARIMA_OK;
+    if (!series || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int K = sts::model_num_params(model);
+    const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
+    const size_t out_bytes = (size_t)N * (want_grad ? K : 1) * sizeof(double);
+    const Span in[2] = {{series, row_bytes}, {params, par_bytes}};
+    const Span o[1] = {{out, out_bytes}};
+    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, h->h_coef.ensure(par_bytes), "staging");
+    RCCHK(h, h->h_aux.ensure(out_bytes), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, params, par_bytes, hipMemcpyHostToDevice, s));
+    RCCHK(h, sts::launch_model_eval(model, h->h_series.as<double>(), T, N, T, h->h_coef.as<double>(),
+                                    want_grad ? nullptr : h->h_aux.as<double>(),
+                                    want_grad ? h->h_aux.as<double>() : nullptr, s), "model eval");
+    HIPCHK(h, hipMemcpyAsync(out, h->h_aux.ptr, out_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+int md_effects_host(arima_handle *h, int model, const double *in_rows, int64_t N, int32_t T, const double *params,
+                    double *out, int add) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0 || T == 0) return ARIMA_OK;
+    if (!in_rows || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int K = sts::model_num_params(model);
+    const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
+    const Span in[2] = {{in_rows, row_bytes}, {params, par_bytes}};
+    const Span o[1] = {{out, row_bytes}};
+    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = h->stream;
+    begin_call(h, s);
+    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
+    RCCHK(h, h->md_out.ensure(row_bytes), "staging");
+    RCCHK(h, h->h_coef.ensure(par_bytes), "staging");
+    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, in_rows, row_bytes, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, params, par_bytes, hipMemcpyHostToDevice, s));
+    RCCHK(h, sts::launch_model_effects(model, h->h_series.as<double>(), T, h->h_coef.as<double>(),
+                                       h->md_out.as<double>(), T, N, T, add, s), "model effects");
+    HIPCHK(h, hipMemcpyAsync(out, h->md_out.ptr, row_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, end_call(h, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    return ARIMA_OK;
+}
+
+int md_effects_device(arima_handle *h, int model, const double *d_in, int64_t N, int32_t T, int64_t ld,
+                      const double *d_params, double *d_out, int64_t ld_out, void *stream, int add) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (N < 0 || T < 0 || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0 || T == 0) return ARIMA_OK;
+    if (!d_in || !d_params || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int K = sts::model_num_params(model);
+    const Span in[2] = {{d_in, ((size_t)(N - 1) * ld + T) * sizeof(double)}, {d_params, (size_t)N * K * sizeof(double)}};
+    const Span o[1] = {{d_out, ((size_t)(N - 1) * ld_out + T) * sizeof(double)}};
+    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
+    HIPCHK(h, hipSetDevice(h->device));
+    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
+    begin_call(h, s);
+    RCCHK(h, sts::launch_model_effects(model, d_in, ld, d_params, d_out, ld_out, N, T, add, s), "model effects");
+    HIPCHK(h, end_call(h, s));
+    return ARIMA_OK;
+}
+}  // namespace
+
+int arima_ewma_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *smoothing_out,
+                         double *sse_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
+    return md_fit_host(h, sts::kModelEwma, series, N, T, smoothing_out, sse_out, status_out, n_eval_out, n_grad_out);
+}
+
+int arima_ewma_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                double *d_smoothing_out, double *d_sse_out, int32_t *d_status_out,
+                                int32_t *d_n_eval_out, int32_t *d_n_grad_out, void *stream) {
+    return md_fit_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing_out, d_sse_out, d_status_out,
+                         d_n_eval_out, d_n_grad_out, stream);
+}
+
+int arima_garch_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *coef_out,
+                          double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
+    return md_fit_host(h, sts::kModelGarch, series, N, T, coef_out, ll_out, status_out, n_eval_out, n_grad_out);
+}
+
+int arima_garch_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                 double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                 int32_t *d_n_grad_out, void *stream) {
+    return md_fit_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
+                         d_n_grad_out, stream);
+}
+
+int arima_ewma_sse_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *smoothing,
+                         double *sse_out) {
+    return md_eval_host(h, sts::kModelEwma, series, N, T, smoothing, sse_out, 0);
+}
+
+int arima_ewma_gradient_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *smoothing,
+                              double *grad_out) {
+    return md_eval_host(h, sts::kModelEwma, series, N, T, smoothing, grad_out, 1);
+}
+
+int arima_garch_loglik_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                             double *ll_out) {
+    return md_eval_host(h, sts::kModelGarch, series, N, T, coef, ll_out, 0);
+}
+
+int arima_garch_gradient_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                               double *grad_out) {
+    return md_eval_host(h, sts::kModelGarch, series, N, T, coef, grad_out, 1);
+}
+
+int arima_ewma_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
+                                    const double *smoothing, double *out) {
+    return md_effects_host(h, sts::kModelEwma, series, N, T, smoothing, out, 0);
+}
+
+int arima_ewma_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *smoothing,
+                                 double *out) {
+    return md_effects_host(h, sts::kModelEwma, series, N, T, smoothing, out, 1);
+}
+
+int arima_garch_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                                     double *out) {
+    return md_effects_host(h, sts::kModelGarch, series, N, T, coef, out, 0);
+}
+
+int arima_garch_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                                  double *out) {
+    return md_effects_host(h, sts::kModelGarch, series, N, T, coef, out, 1);
+}
+
+int arima_ewma_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                           const double *d_smoothing, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing, d_out, ld_out, stream, 0);
+}
+
+int arima_ewma_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                        const double *d_smoothing, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing, d_out, ld_out, stream, 1);
+}
+
+int arima_garch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                            const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 0);
+}
+
+int arima_garch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                         const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 1);
+}
+
+int arima_get_last_model_fit_stats(arima_handle *h, arima_model_fit_stats *out) {
+    if (!h || !out) return ARIMA_E_INVALID_ARG;
+    std::lock_guard<std::mutex> lk(h->mu);
+    memset(out, 0, sizeof *out);
+    if (h->md_last_n < 0) return set_err(h, ARIMA_E_INVALID_ARG, "no EWMA / GARCH fit on this handle yet");
+    HIPCHK(h, hipSetDevice(h->device));
+    if (h->has_done) HIPCHK(h, hipEventSynchronize(h->ev_done));
+    unsigned long long w[sts::kModelCtlWords];
+    HIPCHK(h, hipMemcpy(w, h->md_ctl.ptr, sizeof w, hipMemcpyDeviceToHost));
+    out->n_series = h->md_last_n;
+    out->wave_passes = (int64_t)w[0];
+    out->lane_passes = (int64_t)w[1];
+    out->max_wave_passes = (int64_t)w[2];
     return ARIMA_OK;
 }
 

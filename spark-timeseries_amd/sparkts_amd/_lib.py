@@ -56,7 +56,16 @@ EXPORTED = [
     "arima_add_effects_batch", "arima_add_effects_batch_device",
     "arima_diagnostics_batch", "arima_diagnostics_batch_device", "arima_residual_diagnostics_batch",
     "arima_residual_diagnostics_batch_device",
+    "arima_ewma_fit_batch", "arima_ewma_fit_batch_device", "arima_garch_fit_batch", "arima_garch_fit_batch_device",
+    "arima_ewma_sse_batch", "arima_ewma_gradient_batch", "arima_garch_loglik_batch", "arima_garch_gradient_batch",
+    "arima_ewma_remove_effects_batch", "arima_ewma_add_effects_batch", "arima_garch_remove_effects_batch",
+    "arima_garch_add_effects_batch", "arima_ewma_remove_effects_batch_device", "arima_ewma_add_effects_batch_device",
+    "arima_garch_remove_effects_batch_device", "arima_garch_add_effects_batch_device",
+    "arima_get_last_model_fit_stats",
 ]
+
+# the small models (EWMA.scala, GARCH.scala): parameters per series
+MODEL_PARAMS = {"ewma": 1, "garch": 3}
 
 
 class FitStats(ctypes.Structure):
@@ -81,6 +90,15 @@ class FitStats(ctypes.Structure):
         d["diag"] = list(self.diag)
         d["fault_info"] = list(self.fault_info)
         return d
+
+
+class ModelFitStats(ctypes.Structure):
+    """arima_model_fit_stats: the EWMA / GARCH fit kernel's round counters."""
+    _fields_ = [("n_series", ctypes.c_int64), ("wave_passes", ctypes.c_int64), ("lane_passes", ctypes.c_int64),
+                ("max_wave_passes", ctypes.c_int64)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
 
 
 class EngineError(RuntimeError):
@@ -162,6 +180,17 @@ def load():
                                                        _dp, _dp]
         L.arima_residual_diagnostics_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp,
                                                               _i32, _vp, _vp, _vp, _vp, _vp]
+        for m in ("ewma", "garch"):
+            getattr(L, f"arima_{m}_fit_batch").argtypes = [H, _dp, _i64, _i32, _dp, _dp, _i32p, _i32p, _i32p]
+            getattr(L, f"arima_{m}_fit_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
+            for d in ("remove", "add"):
+                getattr(L, f"arima_{m}_{d}_effects_batch").argtypes = [H, _dp, _i64, _i32, _dp, _dp]
+                getattr(L, f"arima_{m}_{d}_effects_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _vp, _vp, _i64,
+                                                                             _vp]
+        for fn in (L.arima_ewma_sse_batch, L.arima_ewma_gradient_batch, L.arima_garch_loglik_batch,
+                   L.arima_garch_gradient_batch):
+            fn.argtypes = [H, _dp, _i64, _i32, _dp, _dp]
+        L.arima_get_last_model_fit_stats.argtypes = [H, ctypes.POINTER(ModelFitStats)]
         _lib = L
         return L
 
@@ -373,6 +402,114 @@ class Engine:
         self._check(self.L.arima_add_effects_batch_device(self.h, d_noise, n_series, T, ld, p, d, q,
                                                           int(bool(include_intercept)), d_coef, d_out, ld_out,
                                                           stream), "arima_add_effects_batch_device")
+        if blocking:
+            self.synchronize()
+
+    # ---- the small models: EWMA (EWMA.scala) and GARCH(1,1) (GARCH.scala) -------------------------------------
+    @staticmethod
+    def _rows(series):
+        series = np.ascontiguousarray(series, dtype=np.float64)
+        return series[None, :] if series.ndim == 1 else series
+
+    def _model_fit(self, model, series):
+        series = self._rows(series)
+        N, T = series.shape
+        K = MODEL_PARAMS[model]
+        r = dict(coef=np.empty((N, K)), obj=np.empty(N), status=np.empty(N, dtype=np.int32),
+                 n_eval=np.empty(N, dtype=np.int32), n_grad=np.empty(N, dtype=np.int32))
+        name = f"arima_{model}_fit_batch"
+        self._check(getattr(self.L, name)(self.h, _ptr(series), N, T, _ptr(r["coef"]), _ptr(r["obj"]),
+                                          _ptr(r["status"], _i32p), _ptr(r["n_eval"], _i32p),
+                                          _ptr(r["n_grad"], _i32p)), name)
+        return r
+
+    def ewma_fit_batch(self, series):
+        """EWMA.fitModel of every row (EWMA.scala:45-69): dict(smoothing N, sse N, status, n_eval, n_grad)."""
+        r = self._model_fit("ewma", series)
+        return dict(smoothing=r["coef"][:, 0], sse=r["obj"], status=r["status"], n_eval=r["n_eval"],
+                    n_grad=r["n_grad"])
+
+    def garch_fit_batch(self, series):
+        """GARCH.fitModel of every row (GARCH.scala:33-53): dict(coef N x 3 (omega, alpha, beta), ll N, status, n_eval,
+        n_grad)."""
+        r = self._model_fit("garch", series)
+        return dict(coef=r["coef"], ll=r["obj"], status=r["status"], n_eval=r["n_eval"], n_grad=r["n_grad"])
+
+    def _model_fit_device(self, model, d_series, n_series, T, ld, d_coef, d_obj, d_status, d_n_eval, d_n_grad, stream,
+                          blocking):
+        name = f"arima_{model}_fit_batch_device"
+        self._check(getattr(self.L, name)(self.h, d_series, n_series, T, ld, d_coef, d_obj, d_status, d_n_eval,
+                                          d_n_grad, stream), name)
+        if blocking:
+            self.synchronize()
+
+    def ewma_fit_batch_device(self, d_series, n_series, T, ld, d_smoothing, d_sse, d_status, d_n_eval=None,
+                              d_n_grad=None, stream=None, blocking=True):
+        """Device-pointer EWMA fits (ints = raw HBM addresses)."""
+        self._model_fit_device("ewma", d_series, n_series, T, ld, d_smoothing, d_sse, d_status, d_n_eval, d_n_grad,
+                               stream, blocking)
+
+    def garch_fit_batch_device(self, d_series, n_series, T, ld, d_coef, d_ll, d_status, d_n_eval=None, d_n_grad=None,
+                               stream=None, blocking=True):
+        """Device-pointer GARCH fits; d_coef N x 3 (omega, alpha, beta)."""
+        self._model_fit_device("garch", d_series, n_series, T, ld, d_coef, d_ll, d_status, d_n_eval, d_n_grad, stream,
+                               blocking)
+
+    def model_fit_stats(self):
+        """Round counters of the last EWMA / GARCH fit (waits for it): n_series, wave_passes, lane_passes,
+        max_wave_passes."""
+        s = ModelFitStats()
+        self._check(self.L.arima_get_last_model_fit_stats(self.h, ctypes.byref(s)), "arima_get_last_model_fit_stats")
+        return s.as_dict()
+
+    def _model_call(self, name, model, series, params, out_cols):
+        """A building block or an effects call: params (K,) or (N, K), one model per row; out_cols None = N x T."""
+        series = self._rows(series)
+        N, T = series.shape
+        K = MODEL_PARAMS[model]
+        params = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float64).reshape(-1, K), (N, K)))
+        out = np.empty((N, T) if out_cols is None else (N, out_cols))
+        self._check(getattr(self.L, name)(self.h, _ptr(series), N, T, _ptr(params), _ptr(out)), name)
+        return out
+
+    def ewma_sse(self, series, smoothing):
+        """EWMAModel.sse (EWMA.scala:81-96) of every row under its smoothing: (N,)."""
+        return self._model_call("arima_ewma_sse_batch", "ewma", series, smoothing, 1)[:, 0]
+
+    def ewma_gradient(self, series, smoothing):
+        """EWMAModel.gradient (EWMA.scala:102-123), the reference's 2 * dJda: (N,)."""
+        return self._model_call("arima_ewma_gradient_batch", "ewma", series, smoothing, 1)[:, 0]
+
+    def garch_loglik(self, series, coef):
+        """GARCHModel.logLikelihood (GARCH.scala:82-88); coef (3,) or (N, 3) = (omega, alpha, beta): (N,)."""
+        return self._model_call("arima_garch_loglik_batch", "garch", series, coef, 1)[:, 0]
+
+    def garch_gradient(self, series, coef):
+        """GARCHModel.gradient (GARCH.scala:96-115) in the order it returns, (alpha, beta, omega) halves: (N, 3)."""
+        return self._model_call("arima_garch_gradient_batch", "garch", series, coef, 3)
+
+    def ewma_remove_effects(self, series, smoothing):
+        """EWMAModel.removeTimeDependentEffects (EWMA.scala:125-133) of every row: (N, T)."""
+        return self._model_call("arima_ewma_remove_effects_batch", "ewma", series, smoothing, None)
+
+    def ewma_add_effects(self, series, smoothing):
+        """EWMAModel.addTimeDependentEffects (EWMA.scala:135-143), the smoothing recursion: (N, T)."""
+        return self._model_call("arima_ewma_add_effects_batch", "ewma", series, smoothing, None)
+
+    def garch_remove_effects(self, series, coef):
+        """GARCHModel.removeTimeDependentEffects (GARCH.scala:131-145): the standardised series, (N, T)."""
+        return self._model_call("arima_garch_remove_effects_batch", "garch", series, coef, None)
+
+    def garch_add_effects(self, series, coef):
+        """GARCHModel.addTimeDependentEffects (GARCH.scala:147-162): the model driven by the rows, (N, T)."""
+        return self._model_call("arima_garch_add_effects_batch", "garch", series, coef, None)
+
+    def model_effects_device(self, model, direction, d_series, n_series, T, ld, d_params, d_out, ld_out, stream=None,
+                             blocking=True):
+        """Device-pointer TimeSeriesModel pair of model "ewma" / "garch", direction "remove" / "add" (ints = raw HBM
+        addresses; d_params N x K; d_out may not overlap d_series)."""
+        name = f"arima_{model}_{direction}_effects_batch_device"
+        self._check(getattr(self.L, name)(self.h, d_series, n_series, T, ld, d_params, d_out, ld_out, stream), name)
         if blocking:
             self.synchronize()
 

@@ -1,1 +1,3 @@
 from . import ARIMA  # noqa: F401
+from . import EWMA  # noqa: F401
+from . import GARCH  # noqa: F401

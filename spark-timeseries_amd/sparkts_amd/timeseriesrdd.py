@@ -10,6 +10,8 @@ reference would fail the Spark task); `with_status=True` also returns the ARIMA_
 import numpy as np
 
 from .models import ARIMA as _arima
+from .models import EWMA as _ewma
+from .models import GARCH as _garch
 
 
 def fit_arima_partition(records, p, d, q, includeIntercept=True, method="css-cgd", userInitParams=None,
@@ -74,6 +76,40 @@ def arima_diagnostics_partition(records, p, d, q, max_lag, includeIntercept=True
                       float(dg.lb_pvalue[j]), dg.acf[j].copy())
     for rec in out:
         yield rec
+
+
+def _fit_model_partition(fit_models, records, with_status, device):
+    records = list(records)
+    keys = [k for k, _ in records]
+    vals = [np.asarray(v, dtype=np.float64).ravel() for _, v in records]
+    out = [None] * len(records)
+    by_len = {}
+    for i, v in enumerate(vals):
+        by_len.setdefault(len(v), []).append(i)
+    for T, idx in by_len.items():
+        params, status = fit_models(np.stack([vals[i] for i in idx]), device)
+        for j, i in enumerate(idx):
+            out[i] = (keys[i], params[j].copy(), int(status[j]))
+    for rec in out:
+        yield rec if with_status else rec[:2]
+
+
+def fit_ewma_partition(records, with_status=False, device=None):
+    """Partition-level drop-in for `mapSeries(v => Vectors.dense(EWMA.fitModel(v).smoothing))`: records bucketed by
+    length, one ABI call per bucket, back in input order as (key, [smoothing]); NaN for a failed fit."""
+    def fit(batch, dev):
+        r = _ewma.fit_models(batch, device=dev)
+        return r.smoothing[:, None], r.status
+    return _fit_model_partition(fit, records, with_status, device)
+
+
+def fit_garch_partition(records, with_status=False, device=None):
+    """Partition-level drop-in for `mapSeries(v => { val m = GARCH.fitModel(v); Vectors.dense(m.omega, m.alpha,
+    m.beta) })`: (key, [omega, alpha, beta]) in input order; NaNs for a failed fit."""
+    def fit(batch, dev):
+        r = _garch.fit_models(batch, device=dev)
+        return r.coefficients, r.status
+    return _fit_model_partition(fit, records, with_status, device)
 
 
 def map_series_fit_arima(series_by_key, p, d, q, **kw):

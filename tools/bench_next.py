@@ -8,10 +8,14 @@
                 (2,1,2)+c residuals of N x 1024 C2 series: diagnostics_device at max_lag 1, W, W + 1 and 20 and with
                 only dwtest (one pass), residual_diagnostics_device at max_lag W, alternating with
                 remove_effects_device on the same batch in one process, each launch timed with HIP events
+  models        (--models, a run of its own) the small models (EWMA, GARCH(1,1); arima_models.hip) on N x 1024 rows: the
+                four TimeSeriesModel-pair kernels against remove_effects_device at (2,1,2)+c on the same batch
+                (alternating launches, HIP events), then the two fits with the fit kernel's round counters
 Prints one JSON line. Also checks the device-pointer forecast against the host-buffer entry point on 64 rows.
 usage: python tools/bench_next.py [--fc-series N] [--os-series N]
        python tools/bench_next.py --effects [--fx-series N] [--fx-launches K] [--out FILE]
        python tools/bench_next.py --diag [--fx-series N] [--fx-launches K] [--out FILE]
+       python tools/bench_next.py --models [--fx-series N] [--fx-launches K] [--fit-launches K] [--out FILE]
 """
 import argparse
 import json
@@ -171,8 +175,121 @@ def bench_diag(a):
     print(line, flush=True)
 
 
+def bench_models(a):
+    """The small models, device-resident, f64. Effects: the four k_model_effects instances move the bytes of
+    remove_effects_device at (2,1,2)+c (16 N T) with less arithmetic, so the expectation is each median within that
+    call's median plus its spread (max - min) in this run. Fits: no expectation -- ms, series/s and the round counters
+    (wave passes, the slowest wave's passes, the live-lane fraction, the rate passes x 64 x T x 8 B / time)."""
+    import numpy as np
+    import torch
+    import sparkts_amd._lib as L
+    from sparkts_amd import buildinfo
+    eng = L.Engine.get(0)
+    N, T = a.fx_series, 1024
+    dev = torch.device("cuda:0")
+    torch.manual_seed(20261019)
+    gpar = torch.tensor([.2, .3, .5], dtype=torch.float64, device=dev).repeat(N, 1).contiguous()
+    epar = torch.full((N, 1), 0.9, dtype=torch.float64, device=dev)
+    acoef = torch.tensor([8.2, 0.2, 0.5, 0.3, 0.1], dtype=torch.float64, device=dev).repeat(N, 1).contiguous()
+    noise = torch.randn((N, T), dtype=torch.float64, device=dev)
+    g = torch.empty((N, T), dtype=torch.float64, device=dev)     # GARCH(.2, .3, .5) rows: the model over N(0, 1)
+    torch.cuda.synchronize()                                     # the engine's stream does not wait for torch's: randn done
+    eng.model_effects_device("garch", "add", noise.data_ptr(), N, T, T, gpar.data_ptr(), g.data_ptr(), T)
+    o = noise                                                    # the timed effects launches write here
+    ts = torch.cuda.Stream()                                     # see bench_effects
+    stream = ts.cuda_stream
+    assert stream, "need a non-default stream"
+    torch.cuda.synchronize()
+
+    def fx(model, direction, par):
+        return lambda: eng.model_effects_device(model, direction, g.data_ptr(), N, T, T, par.data_ptr(), o.data_ptr(),
+                                                T, stream=stream, blocking=False)
+
+    calls = {
+        "arima_remove": lambda: eng.remove_effects_device(g.data_ptr(), N, T, T, 2, 1, 2, True, acoef.data_ptr(),
+                                                          o.data_ptr(), T, stream=stream, blocking=False),
+        "ewma_remove": fx("ewma", "remove", epar), "ewma_add": fx("ewma", "add", epar),
+        "garch_remove": fx("garch", "remove", gpar), "garch_add": fx("garch", "add", gpar),
+    }
+    for _ in range(3):                                           # warm-up: every kernel loaded, clocks up
+        for f in calls.values():
+            f()
+    torch.cuda.synchronize()
+    ev = {k: [] for k in calls}
+    for _ in range(max(a.fx_launches, 20)):                      # alternating launches, one HIP event pair each
+        for k, f in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            f()
+            e1.record(ts)
+            ev[k].append((e0, e1))
+    torch.cuda.synchronize()
+    out = {"gpu": torch.cuda.get_device_name(0), "series": N, "T": T, "launches_each": len(ev["arima_remove"]),
+           "bytes_per_effects_launch": 16 * N * T, "library_sha": buildinfo.library_sha(),
+           "source_sha": buildinfo.source_sha(), "effects": {}, "fits": {}}
+    for k, pairs in ev.items():
+        ms = np.array([e0.elapsed_time(e1) for e0, e1 in pairs])
+        med = float(np.median(ms))
+        out["effects"][k] = {"median_ms": med, "min_ms": float(ms.min()), "max_ms": float(ms.max()),
+                             "bytes_per_s": 16.0 * N * T / (med * 1e-3)}
+    ref = out["effects"]["arima_remove"]
+    out["effects"]["bound_ms"] = ref["median_ms"] + (ref["max_ms"] - ref["min_ms"])
+    for k in ("ewma_remove", "ewma_add", "garch_remove", "garch_add"):
+        out["effects"][k]["within_bound"] = bool(out["effects"][k]["median_ms"] <= out["effects"]["bound_ms"])
+    print(json.dumps({"progress": "effects", **out["effects"]}), file=sys.stderr, flush=True)
+    # the last timed launch (garch add) equals the host entry point on the first 64 rows
+    host = eng.garch_add_effects(g[:64].cpu().numpy(), (.2, .3, .5))
+    out["device_vs_host_api_identical"] = bool(np.array_equal(host, o[:64].cpu().numpy(), equal_nan=True))
+
+    # fits: EWMA on random walks, GARCH on the rows above
+    torch.cumsum(torch.randn((N, T), dtype=torch.float64, device=dev), dim=1, out=o)
+    torch.cuda.synchronize()                                     # the walks are complete before a fit on another stream reads them
+    par = torch.empty((N, 3), dtype=torch.float64, device=dev)
+    obj = torch.empty(N, dtype=torch.float64, device=dev)
+    st, ne, ng = (torch.empty(N, dtype=torch.int32, device=dev) for _ in range(3))
+    for model, rows in (("ewma", o), ("garch", g)):
+        fit = eng.ewma_fit_batch_device if model == "ewma" else eng.garch_fit_batch_device
+        ms = []
+        for i in range(1 + max(a.fit_launches, 1)):              # the first launch is the warm-up
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(ts)
+            fit(rows.data_ptr(), N, T, T, par.data_ptr(), obj.data_ptr(), st.data_ptr(), ne.data_ptr(), ng.data_ptr(),
+                stream=stream, blocking=False)
+            e1.record(ts)
+            torch.cuda.synchronize()
+            if i:
+                ms.append(e0.elapsed_time(e1))
+            print(json.dumps({"progress": model, "launch": i, "ms": e0.elapsed_time(e1)}), file=sys.stderr, flush=True)
+        ms = np.array(ms)
+        med = float(np.median(ms))
+        c = eng.model_fit_stats()
+        stn, nev = st.cpu().numpy(), ne.cpu().numpy()
+        ok = stn == 0
+        zero_rows = int((rows == 0).all(dim=1).sum())            # guards the inputs: an unfinished row would be all zero
+        out["fits"][model] = {
+            "all_zero_input_rows": zero_rows,
+            "median_ms": med, "min_ms": float(ms.min()), "max_ms": float(ms.max()), "launches": len(ms),
+            "series_per_s": N / (med * 1e-3), "wave_passes": c["wave_passes"], "lane_passes": c["lane_passes"],
+            "max_wave_passes": c["max_wave_passes"], "mean_wave_passes": c["wave_passes"] / ((N + 63) // 64),
+            "live_lane_fraction": c["lane_passes"] / (64.0 * c["wave_passes"]),
+            "tile_rate_bytes_per_s": c["wave_passes"] * 64.0 * T * 8 / (med * 1e-3),
+            "live_row_bytes_per_s": c["lane_passes"] * 1.0 * T * 8 / (med * 1e-3),
+            "status_counts": {str(k): int(v) for k, v in zip(*np.unique(stn, return_counts=True))},
+            "n_eval_ok_median": float(np.median(nev[ok])) if ok.any() else None,
+            "n_eval_ok_p99": float(np.percentile(nev[ok], 99)) if ok.any() else None,
+            "n_eval_ok_max": int(nev[ok].max()) if ok.any() else None}
+    line = json.dumps(out)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+    print(line, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--models", action="store_true", help="measure the EWMA / GARCH effects kernels and fits, only")
+    ap.add_argument("--fit-launches", type=int, default=3, help="--models: timed launches of each fit")
     ap.add_argument("--diag", action="store_true", help="measure the residual diagnostics against remove effects, only")
     ap.add_argument("--effects", action="store_true", help="measure remove / add effects against forecast, only")
     ap.add_argument("--fx-series", type=int, default=1 << 20)
@@ -182,6 +299,9 @@ def main():
     ap.add_argument("--os-series", type=int, default=1 << 16)
     ap.add_argument("--n-future", type=int, default=30)
     a = ap.parse_args()
+    if a.models:
+        bench_models(a)
+        return
     if a.effects:
         bench_effects(a)
         return
