@@ -85,6 +85,8 @@ typedef struct arima_fit_stats {
     int64_t hr_passes;       /* Hannan-Rissanen streaming-QR passes executed                       */
     int64_t n_eval;          /* objective evaluations as counted by the reference (incl. memoised)  */
     int64_t n_grad;          /* gradient evaluations as counted by the reference                    */
+                             /* (both from the css-cgd kernels' counters; after arima_fit_batch also for css-bobyqa and
+                              * the AR-only shortcut, summed from the per-series results; 0 for those after a *_device fit) */
     double  flops;           /* algorithmic flops of all passes executed (SURVEY.md 8(d) formula)   */
     double  ms_difference;   /* device time of each kernel of the last call (HIP events, ms)        */
     double  ms_hr_init;
@@ -134,7 +136,8 @@ int         arima_synchronize(arima_handle *h);
  * Tuning knobs (not part of the reference contract): "smear" (Breeze reading at ARIMA.scala:526, default 1),
  * "fit_pipeline" (fit contexts in rotation for *_device fits, 1..8, default 3), "host_chunk" / "host_pipeline"
  * (series per chunk and contexts of the chunked host path: 131072 / 6 when GPU_MAX_HW_QUEUES >= 8 at arima_create, else
- * 262144 / 3), "host_tail" (1: the host path halves its last chunks), "express_blocks",
+ * 262144 / 3), "host_tail" (1: the host path halves its last chunks, down to 16384 series; a tail chunk never
+ * exceeds "host_chunk", so a "host_chunk" below 16384 keeps its own size to the end), "express_blocks",
  * "grid_blocks", "search_lanes" (in-kernel scheduler and order-search concurrency), "hr_grid" (k_hr_init grid:
  * 0 = a lane per series, > 0 = that
  * many single-wave workgroups, -1 = 1024 for pipelined fits else 0), "fit_slice_bytes"

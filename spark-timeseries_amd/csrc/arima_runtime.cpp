@@ -19,6 +19,7 @@
 
 #include "../../include/sparkts_arima.h"
 #include "arima_launch.hpp"
+#include "host_plan.hpp"
 
 namespace {
 
@@ -196,7 +197,6 @@ struct arima_handle {
     // (host_tail). C2 1M x 1024 from pageable memory, 8 hardware queues: 262144 x 3 contexts 3.86 M series/s,
     // 131072 x 6 4.47-4.65, 65536 x 6 3.65 (profiles/r06/g_e2e); the upload runs at the link's 56 GB/s either way
     // (tools/h2d_bw.py, profiles/r06/d_ab/h2d.json), so the call is bound by the uploads plus its last fit's tail
-    static constexpr int64_t kHostTailMin = 16384;
     int host_pipeline = 3;         // contexts the chunked host path rotates over (option "host_pipeline"; arima_create)
     int64_t host_chunk = 1 << 18;  // series per chunk of the host path (option "host_chunk"; arima_create)
     int host_tail = 1;             // halve the last chunks (option "host_tail")
@@ -270,7 +270,7 @@ int set_err(arima_handle *h, int code, const char *msg) {
         if (rc_ != ARIMA_OK) return set_err((h), rc_, what);                                               \
     } while (0)
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+using sts::plan::round_up;
 // Leading dimension of a differenced-row workspace: 128-B aligned rows of n doubles plus the handle's row_pad
 static int64_t row_stride(const arima_handle *h, int64_t n) { return round_up(std::max<int64_t>(n, 1), 16) + h->row_pad; }
 
@@ -1035,7 +1035,7 @@ int arima_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_se
         for (int j = 0; j < P; ++j) held += h->fctx[j].diff.bytes;
         slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + held) / 10 * 6 / (size_t)std::max(P, 1)));
     }
-    int64_t slice = std::max<int64_t>(1024, slice_bytes / (ldn * (int64_t)sizeof(double)) / 1024 * 1024);
+    int64_t slice = sts::plan::fit_slice_rows(slice_bytes, ldn);
     if (n_series <= slice || T < 0 || ld < T || n_series < 0) {
         const int ci = (int)(h->fit_seq++ % (unsigned)P);
         FitCtx &c = h->fctx[ci];
@@ -1118,17 +1118,7 @@ struct HostOut {
     uint8_t *flags;
 };
 
-// bytes of one chunk's results in pinned staging: coef (n*k), ll, status, n_eval, n_grad, flags
-inline size_t pin_layout(int64_t n, int k, size_t off[6]) {
-    size_t o = 0;
-    off[0] = o; o += round_up((int64_t)n * std::max(k, 1) * 8, 256);
-    off[1] = o; o += round_up(n * 8, 256);
-    off[2] = o; o += round_up(n * 4, 256);
-    off[3] = o; o += round_up(n * 4, 256);
-    off[4] = o; o += round_up(n * 4, 256);
-    off[5] = o; o += round_up(n, 256);
-    return o;
-}
+using sts::plan::pin_layout;   // one chunk's results in pinned staging (host_plan.hpp)
 }  // namespace
 
 static void acc_stats(arima_fit_stats &a, const arima_fit_stats &s) {
@@ -1168,26 +1158,6 @@ static void acc_stats(arima_fit_stats &a, const arima_fit_stats &s) {
     }
 }
 
-// memcpy with `threads` host threads (the caller's pageable rows into a pinned block: one thread copies at a fraction
-// of the host's memory bandwidth, a PCIe Gen5 x16 link needs several)
-static void par_memcpy(void *dst, const void *src, size_t bytes, int threads) {
-    const size_t min_part = size_t(4) << 20;
-    const int t = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), bytes / min_part));
-    if (t <= 1) {
-        memcpy(dst, src, bytes);
-        return;
-    }
-    std::vector<std::thread> pool;
-    const size_t part = (bytes + t - 1) / t / 64 * 64 + 64;
-    for (int i = 0; i < t; ++i) {
-        const size_t off = (size_t)i * part;
-        if (off >= bytes) break;
-        const size_t len = std::min(part, bytes - off);
-        pool.emplace_back([=] { memcpy((char *)dst + off, (const char *)src + off, len); });
-    }
-    for (auto &th : pool) th.join();
-}
-
 // Host rows -> device on stream s through the handle's ring of pinned blocks: block i is filled by the copy threads
 // while block i-1's DMA runs; a block is refilled only after its previous DMA has finished (its event). The caller's
 // buffer is fully read when this returns (as a pageable hipMemcpyAsync's is).
@@ -1207,7 +1177,7 @@ static int upload_staged(arima_handle *h, void *dst, const void *src, size_t byt
             HIPCHK(h, hipEventSynchronize(h->stage_ev[j]));
         }
         const size_t len = std::min(arima_handle::kStageBytes, bytes - off);
-        par_memcpy(h->stage[j], (const char *)src + off, len, h->host_copy_threads);
+        sts::plan::par_memcpy(h->stage[j], (const char *)src + off, len, h->host_copy_threads);
         HIPCHK(h, hipMemcpyAsync((char *)dst + off, h->stage[j], len, hipMemcpyHostToDevice, s));
         HIPCHK(h, hipEventRecord(h->stage_ev[j], s));
         h->stage_used[j] = true;
@@ -1222,12 +1192,27 @@ static int drain_chunk(arima_handle *h, FitCtx &c, int k, const HostOut &o) {
     HIPCHK(h, hipEventSynchronize(c.ev_done));
     const int64_t f = c.chunk_first, n = c.chunk_n;
     c.chunk_n = 0;
-    if (c.pending.valid) finish_stats(h, c);
-    acc_stats(h->host_acc, h->stats);
-    RCCHK(h, check_fault(h, c), "fault");
+    // this chunk's own stats (zeros if its fit left none), never whatever h->stats holds from another chunk
+    const bool kernel_counters = c.pending.valid && c.pending.cg;
+    arima_fit_stats st = compute_stats(c.pending, c.ctl_host, c.ev);
+    c.pending.valid = false;
     size_t off[6];
     pin_layout(n, k, off);
     const char *b = static_cast<const char *>(c.pin);
+    if (!kernel_counters) {
+        // css-bobyqa, the AR-only shortcut and uniform status fills keep no device counters: the evaluation counts are
+        // the sums of the per-series results, which are on the host already
+        const int32_t *ne = reinterpret_cast<const int32_t *>(b + off[3]);
+        const int32_t *ng = reinterpret_cast<const int32_t *>(b + off[4]);
+        st.n_eval = st.n_grad = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            st.n_eval += ne[i];
+            st.n_grad += ng[i];
+        }
+        st.n_series = n;
+    }
+    acc_stats(h->host_acc, st);
+    RCCHK(h, check_fault(h, c), "fault");
     if (k > 0) memcpy(o.coef + f * k, b + off[0], (size_t)n * k * 8);
     memcpy(o.ll + f, b + off[1], (size_t)n * 8);
     memcpy(o.status + f, b + off[2], (size_t)n * 4);
@@ -1251,24 +1236,17 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
     HIPCHK(h, hipSetDevice(h->device));
     const int k = I + p + q;
     const int P = h->host_pipeline;
-    const int64_t chunk = std::min<int64_t>(h->host_chunk, N);
-    // Chunk boundaries: full chunks, then the last two chunks' worth halved again and again (down to 16 384 series).
-    // The call ends with the fit of its last chunk, whose duration is that chunk's slowest series: a small last chunk
-    // exposes less of it after the final upload (C2 1M x 1024 on 8 queues: profiles/r06/g_e2e, h_e2e)
-    std::vector<int64_t> starts;
-    for (int64_t f = 0; f < N;) {
-        starts.push_back(f);
-        const int64_t rem = N - f;
-        int64_t n = std::min(chunk, rem);
-        if (h->host_tail && rem <= 2 * chunk && rem > arima_handle::kHostTailMin) n = std::max<int64_t>(arima_handle::kHostTailMin, (rem + 1) / 2);
-        f += n;
-    }
-    starts.push_back(N);
+    // Chunk boundaries (host_plan.hpp): full chunks, then the last two chunks' worth halved again and again (down to
+    // 16 384 series, never above host_chunk). The call ends with the fit of its last chunk, whose duration is that
+    // chunk's slowest series: a small last chunk exposes less of it after the final upload (C2 1M x 1024 on 8 queues:
+    // profiles/r06/g_e2e, h_e2e). Every buffer below is sized from the plan's largest chunk, whatever the schedule.
+    const std::vector<int64_t> starts = sts::plan::host_chunk_starts(N, h->host_chunk, h->host_tail);
+    const int64_t chunk = sts::plan::max_chunk(starts);
     const int64_t nchunks = (int64_t)starts.size() - 1;
     const int used = (int)std::min<int64_t>(P, nchunks);
     const HostOut o{coef_out, css_ll_out, status_out, n_eval_out, n_grad_out, flags_out};
     h->host_acc = arima_fit_stats{};
-    // every context the call uses: settle what an earlier call left in it, then size its buffers for a full chunk
+    // every context the call uses: settle what an earlier call left in it, then size its buffers for the largest chunk
     for (int j = 0; j < used; ++j) {
         FitCtx &c = h->fctx[j];
         if (c.has_done) HIPCHK(h, hipEventSynchronize(c.ev_done));
@@ -1719,7 +1697,7 @@ int residual_diag_dev(arima_handle *h, const double *d_series, int64_t N, int T,
         HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
         slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->dg_resid.bytes) / 10 * 6));
     }
-    const int64_t slice = std::max<int64_t>(64, slice_bytes / (ldw * (int64_t)sizeof(double)) / 64 * 64);
+    const int64_t slice = sts::plan::diag_slice_rows(slice_bytes, ldw);
     RCCHK(h, h->dg_resid.ensure((size_t)std::min(slice, N) * ldw * sizeof(double)), "residual workspace");
     double *resid = h->dg_resid.as<double>();
     for (int64_t f = 0; f < N; f += slice) {

@@ -1,0 +1,109 @@
+// host_plan.hpp — the host-side sizing arithmetic of arima_runtime.cpp as pure functions: the host path's chunk
+// schedule, the layout of one chunk's results in pinned staging, the partition par_memcpy hands its threads, and the
+// rows per slice of the sliced device fit and of the residual diagnostics. No HIP headers: a CPU program includes this
+// file and sweeps the functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of the formulas.
+#pragma once
+
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <cstring>
+#include <thread>
+#include <utility>
+#include <vector>
+
+namespace sts {
+namespace plan {
+
+// smallest chunk the tail schedule (option "host_tail") cuts
+constexpr int64_t kHostTailMin = 16384;
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
+// Chunk boundaries of the host path (arima_fit_batch): starts[0] = 0, ..., starts.back() = N; chunk j holds the series
+// [starts[j], starts[j + 1]). Full chunks of min(host_chunk, N) series, then (host_tail) the last two chunks' worth
+// halved again and again, down to kHostTailMin series. The call ends with the fit of its last chunk, whose duration
+// is that chunk's slowest series: a small last chunk exposes less of it after the final upload. No chunk exceeds
+// min(host_chunk, N): a host_chunk below kHostTailMin keeps its own size in the tail.
+inline std::vector<int64_t> host_chunk_starts(int64_t N, int64_t host_chunk, int host_tail) {
+    std::vector<int64_t> starts;
+    const int64_t chunk = std::min<int64_t>(std::max<int64_t>(host_chunk, 1), N);
+    for (int64_t f = 0; f < N;) {
+        starts.push_back(f);
+        const int64_t rem = N - f;
+        int64_t n = std::min(chunk, rem);
+        if (host_tail && rem <= 2 * chunk && rem > kHostTailMin)
+            n = std::min(chunk, std::max<int64_t>(kHostTailMin, (rem + 1) / 2));
+        f += n;
+    }
+    starts.push_back(std::max<int64_t>(N, 0));
+    return starts;
+}
+
+// largest chunk of a plan (what every per-context buffer of the host path is sized for)
+inline int64_t max_chunk(const std::vector<int64_t> &starts) {
+    int64_t m = 0;
+    for (size_t j = 0; j + 1 < starts.size(); ++j) m = std::max(m, starts[j + 1] - starts[j]);
+    return m;
+}
+
+// bytes of one chunk's results in pinned staging: coef (n*k), ll, status, n_eval, n_grad, flags
+inline size_t pin_layout(int64_t n, int k, size_t off[6]) {
+    size_t o = 0;
+    off[0] = o; o += round_up((int64_t)n * std::max(k, 1) * 8, 256);
+    off[1] = o; o += round_up(n * 8, 256);
+    off[2] = o; o += round_up(n * 4, 256);
+    off[3] = o; o += round_up(n * 4, 256);
+    off[4] = o; o += round_up(n * 4, 256);
+    off[5] = o; o += round_up(n, 256);
+    return o;
+}
+
+// The (offset, length) pieces par_memcpy copies, one per thread: at most `threads` of them, none below 4 MiB unless
+// it is the only one, every boundary a multiple of 64 bytes.
+inline std::vector<std::pair<size_t, size_t>> memcpy_parts(size_t bytes, int threads) {
+    std::vector<std::pair<size_t, size_t>> parts;
+    const size_t min_part = size_t(4) << 20;
+    const int t = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(threads, 1), bytes / min_part));
+    if (t <= 1) {
+        if (bytes) parts.emplace_back(size_t(0), bytes);
+        return parts;
+    }
+    const size_t part = (bytes + t - 1) / t / 64 * 64 + 64;
+    for (int i = 0; i < t; ++i) {
+        const size_t off = (size_t)i * part;
+        if (off >= bytes) break;
+        parts.emplace_back(off, std::min(part, bytes - off));
+    }
+    return parts;
+}
+
+// memcpy with `threads` host threads (the caller's pageable rows into a pinned block: one thread copies at a fraction
+// of the host's memory bandwidth, a PCIe Gen5 x16 link needs several)
+inline void par_memcpy(void *dst, const void *src, size_t bytes, int threads) {
+    const auto parts = memcpy_parts(bytes, threads);
+    if (parts.size() <= 1) {
+        if (bytes) memcpy(dst, src, bytes);
+        return;
+    }
+    std::vector<std::thread> pool;
+    for (const auto &pt : parts) {
+        const size_t off = pt.first, len = pt.second;
+        pool.emplace_back([=] { memcpy((char *)dst + off, (const char *)src + off, len); });
+    }
+    for (auto &th : pool) th.join();
+}
+
+// rows of one slice of a sliced device fit: whole thousands (1024) of rows of ld_doubles doubles within slice_bytes,
+// at least 1024
+inline int64_t fit_slice_rows(int64_t slice_bytes, int64_t ld_doubles) {
+    return std::max<int64_t>(1024, slice_bytes / (ld_doubles * (int64_t)sizeof(double)) / 1024 * 1024);
+}
+
+// rows of one slice of the residual diagnostics: multiples of 64 rows within slice_bytes, at least 64
+inline int64_t diag_slice_rows(int64_t slice_bytes, int64_t ld_doubles) {
+    return std::max<int64_t>(64, slice_bytes / (ld_doubles * (int64_t)sizeof(double)) / 64 * 64);
+}
+
+}  // namespace plan
+}  // namespace sts
