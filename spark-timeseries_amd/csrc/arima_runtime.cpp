@@ -8,10 +8,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -97,6 +99,7 @@ constexpr int kMaxSearchLanes = sts::kSearchMaxLanes;
 constexpr int kMaxD = 16;
 constexpr int kMaxPipeline = 8;
 constexpr int64_t kBobyqaWaveMaxN = 4096;     // css-bobyqa fits up to this many series: a wave per series
+using sts::plan::ByteSpan;
 
 // One fit context: what a fit call needs for itself (stream, differenced-series workspace, HR init, kernel counters,
 // timing events, pinned counter copy, host-path staging). Fit calls rotate over h->pipeline contexts, so with
@@ -105,7 +108,7 @@ constexpr int64_t kBobyqaWaveMaxN = 4096;     // css-bobyqa fits up to this many
 // One device-fit call's caller buffers as byte ranges [lo, hi) (series rows and user inits read; the six outputs
 // written) -- fit_pipeline > 1 hazard tracking
 struct CallSpans {
-    uintptr_t in[2][2] = {}, out[6][2] = {};
+    ByteSpan in[2], out[6];
 };
 constexpr int kInflightMax = 16;   // tracked calls per context; beyond, every later call waits for that context
 struct Inflight {                  // the device-fit calls on one context that may not have finished yet
@@ -132,15 +135,6 @@ struct FitCtx {
     size_t pin_bytes = 0;
     int64_t chunk_first = -1, chunk_n = 0;    // the chunk whose results wait in `pin`
 };
-
-inline void set_span(uintptr_t (&sp)[2], const void *p, int64_t bytes) {
-    sp[0] = (uintptr_t)p;
-    sp[1] = p && bytes > 0 ? (uintptr_t)p + (uintptr_t)bytes : (uintptr_t)p;
-}
-
-inline bool spans_meet(const uintptr_t (&a)[2], const uintptr_t (&b)[2]) {
-    return a[0] < a[1] && b[0] < b[1] && a[0] < b[1] && b[0] < a[1];
-}
 
 }  // namespace
 
@@ -226,28 +220,26 @@ struct arima_handle {
     // device workspaces of the building blocks
     DevBuf diff;
     DevBuf fc_ws;                  // the runtime-order forecast's per-series arrays (forecast_any)
-    // host-API staging
-    DevBuf h_series, h_coef, h_ll, h_status, h_neval, h_ngrad, h_flags, h_uinit, h_aux;
-    // order search: the differenced series per d, the concurrent fit lanes, host-API staging of the orders
+    // the staged arrays of the host-buffer entry points, one call's at a time (CallFrame::stage)
+    DevBuf staging;
+    // order search: the differenced series per d, the concurrent fit lanes
     DevBuf os_diff[kMaxD + 1];
     hipEvent_t ev_diff[kMaxD + 1] = {};
     SearchLane lanes[kMaxSearchLanes];
-    DevBuf os_order;
     unsigned long long *search_acc_host = nullptr;   // pinned: (kCtlWords + 1) words per lane of the last search
     // autoFit (arima_autofit_batch*): the differenced rows, the walk state, the rounds' per-order lists and results
     DevBuf af_rows, af_dsel, af_state, af_best, af_counts, af_lists, af_off, af_coef, af_ll, af_status, af_flags;
     DevBuf af_init, af_hrst, af_rlist, af_rcount;     // the round's inits and the css-bobyqa retry list
-    DevBuf af_out_order, af_out_coef, af_out_aic, af_out_status, af_out_nfits;   // host-API staging
     int64_t *af_host = nullptr;                      // pinned: kAfCombosMax counts, kAfCombosMax row offsets, the retry count
     hipEvent_t ev_af = nullptr;
     int search_lanes_used = 0;
     int64_t search_n = 0, search_fits = 0;
     int64_t autofit_slice = 0;     // autoFit series per slice (option "autofit_slice"; 0 = from free HBM)
-    // residual diagnostics (arima_residual_diagnostics_batch*): one slice of residuals, and host-API staging of the outputs
+    // residual diagnostics (arima_residual_diagnostics_batch*): one slice of residuals
     int64_t diag_slice_bytes = 0;  // option "diag_slice_bytes"; 0 = 60 % of the free HBM, at least 1 GiB
-    DevBuf dg_resid, dg_acf, dg_dw, dg_lbs, dg_lbp;
-    // the small models (EWMA, GARCH): the fit kernel's counters of the last fit, and host-API staging of N x T outputs
-    DevBuf md_ctl, md_out;
+    DevBuf dg_resid;
+    // the small models (EWMA, GARCH): the fit kernel's counters of the last fit
+    DevBuf md_ctl;
     int64_t md_last_n = -1;        // series of the last EWMA / GARCH fit (-1: none yet)
 };
 
@@ -268,6 +260,13 @@ int set_err(arima_handle *h, int code, const char *msg) {
     do {                                                                                                   \
         int rc_ = (expr);                                                                                  \
         if (rc_ != ARIMA_OK) return set_err((h), rc_, what);                                               \
+    } while (0)
+
+// expr has set the message itself
+#define PASSCHK(expr)                                                                                      \
+    do {                                                                                                   \
+        int rc_ = (expr);                                                                                  \
+        if (rc_ != ARIMA_OK) return rc_;                                                                   \
     } while (0)
 
 using sts::plan::round_up;
@@ -340,6 +339,126 @@ int check_orders(arima_handle *h, int p, int d, int q, int I) {
     if (!sts::gen_orders_ok(p, q)) return set_err(h, ARIMA_E_UNSUPPORTED, "p, q <= 20");
     if (d > 16) return set_err(h, ARIMA_E_UNSUPPORTED, "d <= 16");
     return ARIMA_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Ordering. A non-fit call waits (on the device, not the host) for every earlier call: the building blocks share
+// the handle's workspaces, and any call may read an earlier call's outputs. A fit call waits for the earlier
+// non-fit calls (e.g. the sampler that wrote its input), for the previous call on its own context and, with
+// fit_pipeline > 1 (default 3), for any in-flight fit whose buffers its own overlap (order_after_overlapping_fits);
+// with fit_pipeline = 1 the previous call on its context is the previous fit, so calls run in issue order.
+void begin_call(arima_handle *h, hipStream_t s) {
+    if (h->has_done) hipStreamWaitEvent(s, h->ev_done, 0);
+    for (auto &c : h->fctx)
+        if (c.has_done) hipStreamWaitEvent(s, c.ev_done, 0);
+}
+
+hipError_t end_call(arima_handle *h, hipStream_t s) {
+    hipError_t e = hipEventRecord(h->ev_done, s);
+    if (e == hipSuccess) h->has_done = true;
+    return e;
+}
+
+// One staged array of a host-buffer call: the caller's buffer, its size, and its direction. An input (`up`) is always
+// uploaded and an output (`down`) always downloaded, whatever the pointer: the entry points that do not check their
+// buffers leave a null one to the copy, which refuses it. Only an optional output is skipped when the caller passes
+// null; its region is still there for the kernel to write.
+struct Staged {
+    const void *src;
+    void *dst;
+    size_t bytes;
+    bool up, down;
+};
+inline Staged stage_in(const void *p, size_t bytes) { return {p, nullptr, bytes, true, false}; }
+inline Staged stage_out(void *p, size_t bytes) { return {nullptr, p, bytes, false, true}; }
+inline Staged stage_optional_out(void *p, size_t bytes) { return {nullptr, p, bytes, false, p != nullptr}; }
+inline Staged stage_inout(const void *src, void *dst, size_t bytes) { return {src, dst, bytes, true, true}; }
+
+enum CallFlavour { kDeviceBuffers, kHostBuffers };
+
+// The frame of every non-fit entry point. It holds the handle's lock from construction; the argument checks run under
+// it and touch no device. begin() selects the handle's device, picks the stream and orders it behind every earlier
+// call. From then on every way out -- finish(), or an error return from the middle of the body -- records the call's
+// end event, so later calls wait for whatever this one enqueued, and a host-buffer call also waits for its stream, so
+// no copy into the caller's arrays is in flight when it returns. The first error keeps its code and message.
+class CallFrame {
+  public:
+    CallFrame(arima_handle *h, CallFlavour flavour) : h_(h), lk_(h->mu), host_(flavour == kHostBuffers) {}
+    CallFrame(const CallFrame &) = delete;
+    CallFrame &operator=(const CallFrame &) = delete;
+    ~CallFrame() { close(nullptr); }
+
+    int begin(void *stream = nullptr) {
+        HIPCHK(h_, hipSetDevice(h_->device));
+        s_ = stream ? (hipStream_t)stream : h_->stream;
+        begin_call(h_, s_);
+        open_ = true;
+        return ARIMA_OK;
+    }
+    hipStream_t s() const { return s_; }
+
+    // Lays the call's arrays out in the handle's staging block (sts::plan::arena_layout), grows it once and uploads
+    // the inputs. dev<T>(i) is row i's device copy.
+    int stage(std::initializer_list<Staged> rows) {
+        assert(rows.size() <= (size_t)kMaxStaged);
+        size_t bytes[kMaxStaged];
+        n_ = 0;
+        for (const Staged &r : rows) {
+            row_[n_] = r;
+            bytes[n_++] = r.bytes;
+        }
+        const size_t total = sts::plan::arena_layout(bytes, n_, off_);
+        RCCHK(h_, h_->staging.ensure(std::max<size_t>(total, 256)), "staging");
+        for (int i = 0; i < n_; ++i)
+            if (row_[i].up && row_[i].bytes)
+                HIPCHK(h_, hipMemcpyAsync(at(i), row_[i].src, row_[i].bytes, hipMemcpyHostToDevice, s_));
+        return ARIMA_OK;
+    }
+    template <class T>
+    T *dev(int i) const { return reinterpret_cast<T *>(at(i)); }
+
+    // The way out of a body that got this far: after rc == ARIMA_OK the staged outputs go back to the host; then the
+    // end event and, for host buffers, the wait. Returns the first error.
+    int finish(int rc = ARIMA_OK) {
+        for (int i = 0; i < n_ && rc == ARIMA_OK; ++i) {
+            if (!row_[i].down || !row_[i].bytes) continue;
+            const hipError_t e = hipMemcpyAsync(row_[i].dst, at(i), row_[i].bytes, hipMemcpyDeviceToHost, s_);
+            if (e != hipSuccess) rc = set_err(h_, ARIMA_E_DEVICE, hipGetErrorString(e));
+        }
+        close(&rc);
+        return rc;
+    }
+
+  private:
+    static constexpr int kMaxStaged = 8;
+    char *at(int i) const { return h_->staging.as<char>() + off_[i]; }
+    void close(int *rc) {
+        if (!open_) return;
+        open_ = false;
+        hipError_t e = end_call(h_, s_);
+        if (host_) {
+            const hipError_t w = hipStreamSynchronize(s_);
+            if (e == hipSuccess) e = w;
+        }
+        if (e != hipSuccess && rc && *rc == ARIMA_OK) *rc = set_err(h_, ARIMA_E_DEVICE, hipGetErrorString(e));
+    }
+    arima_handle *h_;
+    std::lock_guard<std::mutex> lk_;
+    const bool host_;
+    hipStream_t s_ = nullptr;
+    bool open_ = false;
+    int n_ = 0;
+    Staged row_[kMaxStaged];
+    size_t off_[kMaxStaged];
+};
+
+// The rule of every entry point that checks its buffers (sts::plan::find_overlap), with its two messages
+int check_overlap(arima_handle *h, std::initializer_list<ByteSpan> in, std::initializer_list<ByteSpan> out) {
+    switch (sts::plan::find_overlap(in.begin(), (int)in.size(), out.begin(), (int)out.size())) {
+    case sts::plan::kOutputMeetsInput: return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
+    case sts::plan::kOutputsMeet: return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
+    default: return ARIMA_OK;
+    }
 }
 
 }  // namespace
@@ -656,24 +775,7 @@ int arima_get_option(const arima_handle *hc, const char *name, int64_t *value) {
     return ARIMA_E_INVALID_ARG;
 }
 
-// ---------------------------------------------------------------------------------------------------------
-// Ordering. A non-fit call waits (on the device, not the host) for every earlier call: the building blocks share
-// the handle's workspaces, and any call may read an earlier call's outputs. A fit call waits for the earlier
-// non-fit calls (e.g. the sampler that wrote its input), for the previous call on its own context and, with
-// fit_pipeline > 1 (default 3), for any in-flight fit whose buffers its own overlap (order_after_overlapping_fits);
-// with fit_pipeline = 1 the previous call on its context is the previous fit, so calls run in issue order.
-static void begin_call(arima_handle *h, hipStream_t s) {
-    if (h->has_done) hipStreamWaitEvent(s, h->ev_done, 0);
-    for (auto &c : h->fctx)
-        if (c.has_done) hipStreamWaitEvent(s, c.ev_done, 0);
-}
-
-static hipError_t end_call(arima_handle *h, hipStream_t s) {
-    hipError_t e = hipEventRecord(h->ev_done, s);
-    if (e == hipSuccess) h->has_done = true;
-    return e;
-}
-
+// a fit call's part of the ordering rules (stated at begin_call)
 static void begin_fit(arima_handle *h, FitCtx &c, hipStream_t s) {
     if (h->has_done) hipStreamWaitEvent(s, h->ev_done, 0);
     if (c.has_done) hipStreamWaitEvent(s, c.ev_done, 0);
@@ -686,13 +788,13 @@ static void begin_fit(arima_handle *h, FitCtx &c, hipStream_t s) {
 static bool calls_meet(const CallSpans &x, const CallSpans &y) {
     for (int a = 0; a < 6; ++a) {
         for (int b = 0; b < 2; ++b)
-            if (spans_meet(x.out[a], y.in[b])) return true;
+            if (x.out[a].meets(y.in[b])) return true;
         for (int b = 0; b < 6; ++b)
-            if (spans_meet(x.out[a], y.out[b])) return true;
+            if (x.out[a].meets(y.out[b])) return true;
     }
     for (int a = 0; a < 2; ++a)
         for (int b = 0; b < 6; ++b)
-            if (spans_meet(x.in[a], y.out[b])) return true;
+            if (x.in[a].meets(y.out[b])) return true;
     return false;
 }
 
@@ -731,14 +833,14 @@ static CallSpans call_spans(const double *series, int64_t N, int32_t T, int64_t 
                             const int32_t *ng, const uint8_t *fl) {
     CallSpans cs;
     if (N <= 0) return cs;
-    set_span(cs.in[0], series, ((N - 1) * ld + std::max<int64_t>(T, 0)) * (int64_t)sizeof(double));
-    set_span(cs.in[1], uinit, N * k * (int64_t)sizeof(double));
-    set_span(cs.out[0], coef, N * k * (int64_t)sizeof(double));
-    set_span(cs.out[1], ll, N * (int64_t)sizeof(double));
-    set_span(cs.out[2], st, N * (int64_t)sizeof(int32_t));
-    set_span(cs.out[3], ne, N * (int64_t)sizeof(int32_t));
-    set_span(cs.out[4], ng, N * (int64_t)sizeof(int32_t));
-    set_span(cs.out[5], fl, N);
+    cs.in[0] = ByteSpan(series, ((N - 1) * ld + std::max<int64_t>(T, 0)) * (int64_t)sizeof(double));
+    cs.in[1] = ByteSpan(uinit, N * k * (int64_t)sizeof(double));
+    cs.out[0] = ByteSpan(coef, N * k * (int64_t)sizeof(double));
+    cs.out[1] = ByteSpan(ll, N * (int64_t)sizeof(double));
+    cs.out[2] = ByteSpan(st, N * (int64_t)sizeof(int32_t));
+    cs.out[3] = ByteSpan(ne, N * (int64_t)sizeof(int32_t));
+    cs.out[4] = ByteSpan(ng, N * (int64_t)sizeof(int32_t));
+    cs.out[5] = ByteSpan(fl, N);
     return cs;
 }
 
@@ -1321,40 +1423,26 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
 // ---------------------------------------------------------------------------------------------------------
 int arima_difference_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t d, double *out) {
     if (!h || N < 0 || T < 0 || d < 0) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N == 0 || T == 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     const size_t bytes = (size_t)N * T * sizeof(double);
-    RCCHK(h, h->h_series.ensure(bytes), "staging");
-    RCCHK(h, h->h_aux.ensure(bytes), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_difference(h->h_series.as<double>(), T, h->h_aux.as<double>(), T, N, T, d, 0, s), "difference");
-    HIPCHK(h, hipMemcpyAsync(out, h->h_aux.ptr, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    PASSCHK(f.stage({stage_in(series, bytes), stage_out(out, bytes)}));
+    RCCHK(h, sts::launch_difference(f.dev<double>(0), T, f.dev<double>(1), T, N, T, d, 0, f.s()), "difference");
+    return f.finish();
 }
 
 int arima_inverse_difference_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t d,
                                    double *out) {
     if (!h || N < 0 || T < 0 || d < 0) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N == 0 || T == 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     const size_t bytes = (size_t)N * T * sizeof(double);
-    RCCHK(h, h->h_series.ensure(bytes), "staging");
-    RCCHK(h, h->h_aux.ensure(bytes), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_inverse_difference(h->h_series.as<double>(), T, h->h_aux.as<double>(), T, N, T, d, s),
+    PASSCHK(f.stage({stage_in(series, bytes), stage_out(out, bytes)}));
+    RCCHK(h, sts::launch_inverse_difference(f.dev<double>(0), T, f.dev<double>(1), T, N, T, d, f.s()),
           "inverse_difference");
-    HIPCHK(h, hipMemcpyAsync(out, h->h_aux.ptr, bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    return f.finish();
 }
 
 // upload N rows of length n into the padded (ld multiple of 16) workspace h->diff
@@ -1371,97 +1459,69 @@ static int upload_padded(arima_handle *h, const double *src, int64_t N, int32_t 
 int arima_css_loglik_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p, int32_t d,
                            int32_t q, int32_t I, const double *coef, double *ll_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     const int k = I + p + q;
     const int n = std::max(T - d, 0);
     const int64_t ldn = row_stride(h, n);
-    RCCHK(h, h->h_series.ensure((size_t)N * std::max(T, 1) * sizeof(double)), "staging");
     RCCHK(h, h->diff.ensure((size_t)N * ldn * sizeof(double)), "workspace");
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_ll.ensure((size_t)N * sizeof(double)), "staging");
-    if (T > 0) HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice, s));
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_difference(h->h_series.as<double>(), T, h->diff.as<double>(), ldn, N, T, d, 1, s), "difference");
-    RCCHK(h, sts::launch_css_loglik(h->diff.as<double>(), ldn, n, N, p, q, I, h->h_coef.as<double>(),
-                                    h->h_ll.as<double>(), s), "css_loglik");
-    HIPCHK(h, hipMemcpyAsync(ll_out, h->h_ll.ptr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    PASSCHK(f.stage({stage_in(series, (size_t)N * T * sizeof(double)), stage_in(coef, (size_t)N * k * sizeof(double)),
+                     stage_out(ll_out, (size_t)N * sizeof(double))}));
+    RCCHK(h, sts::launch_difference(f.dev<double>(0), T, h->diff.as<double>(), ldn, N, T, d, 1, f.s()), "difference");
+    RCCHK(h, sts::launch_css_loglik(h->diff.as<double>(), ldn, n, N, p, q, I, f.dev<double>(1), f.dev<double>(2),
+                                    f.s()), "css_loglik");
+    return f.finish();
 }
 
 int arima_css_gradient_batch(arima_handle *h, const double *diffed, int64_t N, int32_t n, int32_t p, int32_t q,
                              int32_t I, const double *coef, double *grad_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, 0, q, I), "orders");
     if (N < 0 || n < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     const int k = I + p + q;
     if (N == 0 || k == 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     int64_t ld = 0;
-    RCCHK(h, upload_padded(h, diffed, N, n, &ld, s), "upload");
-    RCCHK(h, h->h_coef.ensure((size_t)N * k * sizeof(double)), "staging");
-    RCCHK(h, h->h_aux.ensure((size_t)N * k * sizeof(double)), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_css_grad(h->diff.as<double>(), ld, n, N, p, q, I, h->smear, h->h_coef.as<double>(),
-                                  h->h_aux.as<double>(), s), "css_grad");
-    HIPCHK(h, hipMemcpyAsync(grad_out, h->h_aux.ptr, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, upload_padded(h, diffed, N, n, &ld, f.s()), "upload");
+    const size_t coef_bytes = (size_t)N * k * sizeof(double);
+    PASSCHK(f.stage({stage_in(coef, coef_bytes), stage_out(grad_out, coef_bytes)}));
+    RCCHK(h, sts::launch_css_grad(h->diff.as<double>(), ld, n, N, p, q, I, h->smear, f.dev<double>(0), f.dev<double>(1),
+                                  f.s()), "css_grad");
+    return f.finish();
 }
 
 int arima_hannan_rissanen_batch(arima_handle *h, const double *diffed, int64_t N, int32_t n, int32_t p, int32_t q,
                                 int32_t I, double *init_out, int32_t *status_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, 0, q, I), "orders");
     if (N < 0 || n < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     const int k = I + p + q;
     int64_t ld = 0;
-    RCCHK(h, upload_padded(h, diffed, N, n, &ld, s), "upload");
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_status.ensure((size_t)N * sizeof(int32_t)), "staging");
-    RCCHK(h, sts::launch_hr_init(h->diff.as<double>(), ld, n, N, p, q, I, h->h_coef.as<double>(),
-                                 h->h_status.as<int32_t>(), s, std::max(h->hr_grid, 0)), "hr_init");
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(init_out, h->h_coef.ptr, (size_t)N * k * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(status_out, h->h_status.ptr, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, upload_padded(h, diffed, N, n, &ld, f.s()), "upload");
+    PASSCHK(f.stage({stage_out(init_out, (size_t)N * k * sizeof(double)),
+                     stage_out(status_out, (size_t)N * sizeof(int32_t))}));
+    RCCHK(h, sts::launch_hr_init(h->diff.as<double>(), ld, n, N, p, q, I, f.dev<double>(0), f.dev<int32_t>(1), f.s(),
+                                 std::max(h->hr_grid, 0)), "hr_init");
+    return f.finish();
 }
 
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t N, int32_t p, int32_t q, int32_t I,
                             uint8_t *flags_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, 0, q, I), "orders");
     if (N <= 0) return ARIMA_OK;
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    const int k = I + p + q;
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_flags.ensure((size_t)N), "staging");
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_model_flags(h->h_coef.as<double>(), N, p, q, I, h->h_flags.as<uint8_t>(), s), "flags");
-    HIPCHK(h, hipMemcpyAsync(flags_out, h->h_flags.ptr, (size_t)N, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(coef, (size_t)N * (I + p + q) * sizeof(double)), stage_out(flags_out, (size_t)N)}));
+    RCCHK(h, sts::launch_model_flags(f.dev<double>(0), N, p, q, I, f.dev<uint8_t>(1), f.s()), "flags");
+    return f.finish();
 }
 
 // ARIMAModel.forecast over a device batch: k_forecast (p, q <= 5, d <= 8, the streaming kernel) or the runtime-order
@@ -1484,46 +1544,35 @@ static int forecast_any(arima_handle *h, const double *ts, int64_t ld, const dou
 int arima_forecast_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p, int32_t d,
                          int32_t q, int32_t I, const double *coef, int32_t n_future, double *out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     if (N < 0 || T < d || n_future < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!series || !coef || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
+    PASSCHK(f.begin());
     const int k = I + p + q;
     const int64_t L = (int64_t)T + n_future;
-    RCCHK(h, h->h_series.ensure((size_t)N * std::max(T, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_aux.ensure((size_t)N * std::max<int64_t>(L, 1) * sizeof(double)), "staging");
-    if (T > 0) HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice, s));
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
-    RCCHK(h, forecast_any(h, h->h_series.as<double>(), T, h->h_coef.as<double>(), k, h->h_aux.as<double>(), L, N,
-                                  T, p, d, q, I, n_future, s), "forecast");
-    if (L > 0) HIPCHK(h, hipMemcpyAsync(out, h->h_aux.ptr, (size_t)N * L * sizeof(double), hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    PASSCHK(f.stage({stage_in(series, (size_t)N * T * sizeof(double)), stage_in(coef, (size_t)N * k * sizeof(double)),
+                     stage_out(out, (size_t)N * L * sizeof(double))}));
+    RCCHK(h, forecast_any(h, f.dev<double>(0), T, f.dev<double>(1), k, f.dev<double>(2), L, N, T, p, d, q, I, n_future,
+                          f.s()), "forecast");
+    return f.finish();
 }
 
 int arima_forecast_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                 int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef, int32_t n_future,
                                 double *d_out, int64_t ld_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     if (N < 0 || T < d || n_future < 0 || ld < T || ld_out < (int64_t)T + n_future)
         return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!d_series || !d_coef || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, forecast_any(h, d_series, ld, d_coef, I + p + q, d_out, ld_out, N, T, p, d, q, I, n_future, s),
+    PASSCHK(f.begin(stream));
+    RCCHK(h, forecast_any(h, d_series, ld, d_coef, I + p + q, d_out, ld_out, N, T, p, d, q, I, n_future, f.s()),
           "forecast");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    return f.finish();
 }
 
 // ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects over a device batch: k_effects (p, q <= 5, d <= 8,
@@ -1535,62 +1584,51 @@ static int effects_any(const double *in, int64_t ld, const double *coef, int k, 
     return sts::launch_gen_effects(in, ld, coef, k, out, ld_out, N, T, p, d, q, I, add, s);
 }
 
-static bool spans_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a_bytes > 0 && b_bytes > 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+// The ARIMA effects pair may run in place (`aliased`: the output IS the input, same start and stride); any other
+// meeting of the output with the rows or the coefficients is refused.
+static int effects_overlap(arima_handle *h, ByteSpan in, ByteSpan coef, ByteSpan out, bool aliased) {
+    const ByteSpan ins[2] = {aliased ? ByteSpan() : in, coef};
+    if (sts::plan::find_overlap(ins, 2, &out, 1)) return set_err(h, ARIMA_E_INVALID_ARG, "out overlaps an input");
+    return ARIMA_OK;
 }
 
 static int effects_host(arima_handle *h, const double *in, int64_t N, int32_t T, int32_t p, int32_t d, int32_t q,
                         int32_t I, const double *coef, double *out, int add) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     if (N < 0 || T < d) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0 || T == 0) return ARIMA_OK;
     const int k = I + p + q;
     if (!in || (!coef && k > 0) || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t row_bytes = (size_t)N * T * sizeof(double);
-    if ((out != in && spans_meet(in, row_bytes, out, row_bytes)) ||
-        spans_meet(coef, (size_t)N * k * sizeof(double), out, row_bytes))
-        return set_err(h, ARIMA_E_INVALID_ARG, "out overlaps an input");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, in, row_bytes, hipMemcpyHostToDevice, s));
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
+    const size_t row_bytes = (size_t)N * T * sizeof(double), coef_bytes = (size_t)N * k * sizeof(double);
+    PASSCHK(effects_overlap(h, ByteSpan(in, row_bytes), ByteSpan(coef, coef_bytes), ByteSpan(out, row_bytes),
+                            out == in));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_inout(in, out, row_bytes), stage_in(coef, coef_bytes)}));
     // in place on the staged rows: every wave reads a tile before it writes it
-    RCCHK(h, effects_any(h->h_series.as<double>(), T, h->h_coef.as<double>(), k, h->h_series.as<double>(), T, N, T, p,
-                         d, q, I, add, s), "effects");
-    HIPCHK(h, hipMemcpyAsync(out, h->h_series.ptr, row_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, effects_any(f.dev<double>(0), T, f.dev<double>(1), k, f.dev<double>(0), T, N, T, p, d, q, I, add, f.s()),
+          "effects");
+    return f.finish();
 }
 
 static int effects_device(arima_handle *h, const double *d_in, int64_t N, int32_t T, int64_t ld, int32_t p, int32_t d,
                           int32_t q, int32_t I, const double *d_coef, double *d_out, int64_t ld_out, void *stream,
                           int add) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     if (N < 0 || T < d || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0 || T == 0) return ARIMA_OK;
     const int k = I + p + q;
     if (!d_in || (!d_coef && k > 0) || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t in_bytes = ((size_t)(N - 1) * ld + T) * sizeof(double);
-    const size_t out_bytes = ((size_t)(N - 1) * ld_out + T) * sizeof(double);
-    const bool in_place = d_out == d_in && ld_out == ld;
-    if ((!in_place && spans_meet(d_in, in_bytes, d_out, out_bytes)) ||
-        spans_meet(d_coef, (size_t)N * k * sizeof(double), d_out, out_bytes))
-        return set_err(h, ARIMA_E_INVALID_ARG, "out overlaps an input");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, effects_any(d_in, ld, d_coef, k, d_out, ld_out, N, T, p, d, q, I, add, s), "effects");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    PASSCHK(effects_overlap(h, ByteSpan(d_in, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
+                            ByteSpan(d_coef, N * k * (int64_t)sizeof(double)),
+                            ByteSpan(d_out, ((N - 1) * ld_out + T) * (int64_t)sizeof(double)),
+                            d_out == d_in && ld_out == ld));
+    PASSCHK(f.begin(stream));
+    RCCHK(h, effects_any(d_in, ld, d_coef, k, d_out, ld_out, N, T, p, d, q, I, add, f.s()), "effects");
+    return f.finish();
 }
 
 int arima_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p, int32_t d,
@@ -1639,51 +1677,19 @@ int diag_check(arima_handle *h, int64_t N, int32_t T, int32_t max_lag, const Dia
     return ARIMA_OK;
 }
 
-// no output may meet an input range or another output
-int diag_overlap(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, const void *in0, size_t in0_bytes,
-                 const void *in1, size_t in1_bytes) {
-    const void *ptr[4] = {o.acf, o.dw, o.lbs, o.lbp};
-    const size_t len[4] = {o.acf ? (size_t)N * max_lag * sizeof(double) : 0, o.dw ? (size_t)N * sizeof(double) : 0,
-                           o.lbs ? (size_t)N * sizeof(double) : 0, o.lbp ? (size_t)N * sizeof(double) : 0};
-    for (int a = 0; a < 4; ++a) {
-        if (!ptr[a]) continue;
-        if (::spans_meet(in0, in0_bytes, ptr[a], len[a]) || ::spans_meet(in1, in1_bytes, ptr[a], len[a]))
-            return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
-        for (int b = a + 1; b < 4; ++b)
-            if (ptr[b] && ::spans_meet(ptr[a], len[a], ptr[b], len[b]))
-                return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
-    }
-    return ARIMA_OK;
+// the four outputs (a null one is an empty span) against the call's input ranges
+int diag_spans(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, ByteSpan in0, ByteSpan in1) {
+    const int64_t nd = N * (int64_t)sizeof(double);
+    return check_overlap(h, {in0, in1},
+                         {ByteSpan(o.acf, nd * max_lag), ByteSpan(o.dw, nd), ByteSpan(o.lbs, nd), ByteSpan(o.lbp, nd)});
 }
 
-// device staging of the host entry points' outputs
-int diag_stage(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, DiagOut *dev) {
-    *dev = DiagOut{nullptr, nullptr, nullptr, nullptr};
-    if (o.acf) {
-        RCCHK(h, h->dg_acf.ensure((size_t)N * max_lag * sizeof(double)), "staging");
-        dev->acf = h->dg_acf.as<double>();
-    }
-    if (o.dw) {
-        RCCHK(h, h->dg_dw.ensure((size_t)N * sizeof(double)), "staging");
-        dev->dw = h->dg_dw.as<double>();
-    }
-    if (o.lbs) {
-        RCCHK(h, h->dg_lbs.ensure((size_t)N * sizeof(double)), "staging");
-        dev->lbs = h->dg_lbs.as<double>();
-    }
-    if (o.lbp) {
-        RCCHK(h, h->dg_lbp.ensure((size_t)N * sizeof(double)), "staging");
-        dev->lbp = h->dg_lbp.as<double>();
-    }
-    return ARIMA_OK;
-}
-
-int diag_unstage(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, const DiagOut &dev, hipStream_t s) {
-    if (o.acf) HIPCHK(h, hipMemcpyAsync(o.acf, dev.acf, (size_t)N * max_lag * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (o.dw) HIPCHK(h, hipMemcpyAsync(o.dw, dev.dw, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (o.lbs) HIPCHK(h, hipMemcpyAsync(o.lbs, dev.lbs, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (o.lbp) HIPCHK(h, hipMemcpyAsync(o.lbp, dev.lbp, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    return ARIMA_OK;
+// The host entry points stage the four outputs as rows first .. first + 3 of the call's table; one the caller does
+// not want takes no bytes there and stays null for the kernel.
+size_t wanted(const void *out, size_t bytes) { return out ? bytes : 0; }
+DiagOut staged_outputs(const CallFrame &f, const DiagOut &o, int first) {
+    return {o.acf ? f.dev<double>(first) : nullptr, o.dw ? f.dev<double>(first + 1) : nullptr,
+            o.lbs ? f.dev<double>(first + 2) : nullptr, o.lbp ? f.dev<double>(first + 3) : nullptr};
 }
 
 // removeTimeDependentEffects into a bounded workspace slice, then the diagnostics of that slice, slice by slice
@@ -1714,54 +1720,47 @@ int residual_diag_dev(arima_handle *h, const double *d_series, int64_t N, int T,
 int arima_diagnostics_batch(arima_handle *h, const double *rows, int64_t N, int32_t T, int32_t max_lag,
                             double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
     bool done;
     RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
     if (done) return ARIMA_OK;
     if (!rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t row_bytes = (size_t)N * T * sizeof(double);
-    RCCHK(h, diag_overlap(h, N, max_lag, o, rows, row_bytes, nullptr, 0), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    DiagOut dev;
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, diag_stage(h, N, max_lag, o, &dev), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, rows, row_bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_diag(h->h_series.as<double>(), T, N, T, max_lag, dev.acf, dev.dw, dev.lbs, dev.lbp, s),
+    const size_t row_bytes = (size_t)N * T * sizeof(double), nd = (size_t)N * sizeof(double);
+    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(rows, row_bytes), ByteSpan()), "overlap");
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(rows, row_bytes), stage_optional_out(o.acf, wanted(o.acf, nd * max_lag)),
+                     stage_optional_out(o.dw, wanted(o.dw, nd)), stage_optional_out(o.lbs, wanted(o.lbs, nd)),
+                     stage_optional_out(o.lbp, wanted(o.lbp, nd))}));
+    const DiagOut dev = staged_outputs(f, o, 1);
+    RCCHK(h, sts::launch_diag(f.dev<double>(0), T, N, T, max_lag, dev.acf, dev.dw, dev.lbs, dev.lbp, f.s()),
           "diagnostics");
-    RCCHK(h, diag_unstage(h, N, max_lag, o, dev, s), "copy");
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    return f.finish();
 }
 
 int arima_diagnostics_batch_device(arima_handle *h, const double *d_rows, int64_t N, int32_t T, int64_t ld,
                                    int32_t max_lag, double *d_acf_out, double *d_dw_out, double *d_lb_stat_out,
                                    double *d_lb_pvalue_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
     if (ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     bool done;
     RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
     if (done) return ARIMA_OK;
     if (!d_rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    RCCHK(h, diag_overlap(h, N, max_lag, o, d_rows, ((size_t)(N - 1) * ld + T) * sizeof(double), nullptr, 0), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, sts::launch_diag(d_rows, ld, N, T, max_lag, o.acf, o.dw, o.lbs, o.lbp, s), "diagnostics");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(d_rows, ((N - 1) * ld + T) * (int64_t)sizeof(double)), ByteSpan()),
+          "overlap");
+    PASSCHK(f.begin(stream));
+    RCCHK(h, sts::launch_diag(d_rows, ld, N, T, max_lag, o.acf, o.dw, o.lbs, o.lbp, f.s()), "diagnostics");
+    return f.finish();
 }
 
 int arima_residual_diagnostics_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
                                      int32_t d, int32_t q, int32_t I, const double *coef, int32_t max_lag,
                                      double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
     if (T < d) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
@@ -1770,23 +1769,16 @@ int arima_residual_diagnostics_batch(arima_handle *h, const double *series, int6
     if (done) return ARIMA_OK;
     const int k = I + p + q;
     if (!series || (!coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t row_bytes = (size_t)N * T * sizeof(double);
-    RCCHK(h, diag_overlap(h, N, max_lag, o, series, row_bytes, coef, (size_t)N * k * sizeof(double)), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    DiagOut dev;
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, h->h_coef.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "staging");
-    RCCHK(h, diag_stage(h, N, max_lag, o, &dev), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
-    if (k > 0) HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, coef, (size_t)N * k * sizeof(double), hipMemcpyHostToDevice, s));
-    RCCHK(h, residual_diag_dev(h, h->h_series.as<double>(), N, T, T, p, d, q, I, h->h_coef.as<double>(), max_lag, dev, s),
-          "residual diagnostics");
-    RCCHK(h, diag_unstage(h, N, max_lag, o, dev, s), "copy");
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    const size_t row_bytes = (size_t)N * T * sizeof(double), coef_bytes = (size_t)N * k * sizeof(double),
+                 nd = (size_t)N * sizeof(double);
+    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(series, row_bytes), ByteSpan(coef, coef_bytes)), "overlap");
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(coef, coef_bytes),
+                     stage_optional_out(o.acf, wanted(o.acf, nd * max_lag)), stage_optional_out(o.dw, wanted(o.dw, nd)),
+                     stage_optional_out(o.lbs, wanted(o.lbs, nd)), stage_optional_out(o.lbp, wanted(o.lbp, nd))}));
+    RCCHK(h, residual_diag_dev(h, f.dev<double>(0), N, T, T, p, d, q, I, f.dev<double>(1), max_lag,
+                               staged_outputs(f, o, 2), f.s()), "residual diagnostics");
+    return f.finish();
 }
 
 int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
@@ -1794,7 +1786,7 @@ int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_ser
                                             int32_t max_lag, double *d_acf_out, double *d_dw_out,
                                             double *d_lb_stat_out, double *d_lb_pvalue_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
     const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
     if (T < d || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
@@ -1803,14 +1795,11 @@ int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_ser
     if (done) return ARIMA_OK;
     const int k = I + p + q;
     if (!d_series || (!d_coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    RCCHK(h, diag_overlap(h, N, max_lag, o, d_series, ((size_t)(N - 1) * ld + T) * sizeof(double), d_coef,
-                          (size_t)N * k * sizeof(double)), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, residual_diag_dev(h, d_series, N, T, ld, p, d, q, I, d_coef, max_lag, o, s), "residual diagnostics");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
+                        ByteSpan(d_coef, N * k * (int64_t)sizeof(double))), "overlap");
+    PASSCHK(f.begin(stream));
+    RCCHK(h, residual_diag_dev(h, d_series, N, T, ld, p, d, q, I, d_coef, max_lag, o, f.s()), "residual diagnostics");
+    return f.finish();
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2027,42 +2016,30 @@ int arima_order_search_batch_device(arima_handle *h, const double *d_series, int
                                     int32_t intercept_mode, int32_t method, int32_t *d_order_out,
                                     double *d_coef_out, double *d_aic_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
+    CallFrame f(h, kDeviceBuffers);
+    PASSCHK(f.begin(stream));
     const int rc = order_search_locked(h, d_series, n_series, T, ld, max_p, max_d, max_q, intercept_mode, method,
-                                       d_order_out, d_coef_out, d_aic_out, nullptr, s);
-    join_lanes(h, s);
-    HIPCHK(h, end_call(h, s));
-    return rc;
+                                       d_order_out, d_coef_out, d_aic_out, nullptr, f.s());
+    join_lanes(h, f.s());
+    return f.finish(rc);
 }
 
 int arima_order_search_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t max_p,
                              int32_t max_d, int32_t max_q, int32_t intercept_mode, int32_t method,
                              int32_t *order_out, double *coef_out, double *aic_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!series || !order_out || !coef_out || !aic_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure((size_t)N * std::max(T, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->h_aux.ensure((size_t)N * 11 * sizeof(double)), "staging");
-    RCCHK(h, h->h_ll.ensure((size_t)N * sizeof(double)), "staging");
-    RCCHK(h, h->os_order.ensure((size_t)N * 4 * sizeof(int32_t)), "staging");
-    if (T > 0) HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice, s));
-    int rc = order_search_locked(h, h->h_series.as<double>(), N, T, T, max_p, max_d, max_q, intercept_mode, method,
-                                 h->os_order.as<int32_t>(), h->h_aux.as<double>(), h->h_ll.as<double>(), nullptr, s);
-    join_lanes(h, s);
-    if (rc == ARIMA_OK) {
-        HIPCHK(h, hipMemcpyAsync(order_out, h->os_order.ptr, (size_t)N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(coef_out, h->h_aux.ptr, (size_t)N * 11 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(aic_out, h->h_ll.ptr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    PASSCHK(f.begin());
+    const size_t nd = (size_t)N * sizeof(double);
+    PASSCHK(f.stage({stage_in(series, nd * T), stage_out(order_out, (size_t)N * 4 * sizeof(int32_t)),
+                     stage_out(coef_out, 11 * nd), stage_out(aic_out, nd)}));
+    int rc = order_search_locked(h, f.dev<double>(0), N, T, T, max_p, max_d, max_q, intercept_mode, method,
+                                 f.dev<int32_t>(1), f.dev<double>(2), f.dev<double>(3), nullptr, f.s());
+    join_lanes(h, f.s());
+    rc = f.finish(rc);
     if (rc != ARIMA_OK) return rc;
     return take_fault(h);
 }
@@ -2267,17 +2244,15 @@ int arima_autofit_batch_device(arima_handle *h, const double *d_series, int64_t 
                                double *d_coef_out, double *d_aic_out, int32_t *d_status_out, int32_t *d_n_fits_out,
                                void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
-    HIPCHK(h, hipSetDevice(h->device));          // before any stream work
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    const int rc = autofit_locked(h, d_series, n_series, T, ld, max_p, max_d, max_q, d_order_out, d_coef_out,
-                                  d_aic_out, d_status_out, d_n_fits_out, s, nullptr);
-    HIPCHK(h, end_call(h, s));
+    CallFrame f(h, kDeviceBuffers);
+    PASSCHK(f.begin(stream));                    // the device is selected before any stream work
+    int rc = autofit_locked(h, d_series, n_series, T, ld, max_p, max_d, max_q, d_order_out, d_coef_out, d_aic_out,
+                            d_status_out, d_n_fits_out, f.s(), nullptr);
+    rc = f.finish(rc);
     // the walk synchronised with the device once per round, so its fits have finished: a watchdog fault that one of
     // them recorded is reported by this call, not by a later unrelated one
     if (rc != ARIMA_OK) return rc;
-    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipStreamSynchronize(f.s()));
     return take_fault(h);
 }
 
@@ -2285,55 +2260,35 @@ int arima_autofit_batch(arima_handle *h, const double *series, int64_t N, int32_
                         int32_t max_q, int32_t *order_out, double *coef_out, double *aic_out, int32_t *status_out,
                         int32_t *n_fits_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!series || !order_out || !coef_out || !aic_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure((size_t)N * std::max(T, 1) * sizeof(double)), "staging");
-    RCCHK(h, h->af_out_order.ensure((size_t)N * 4 * sizeof(int32_t)), "staging");
-    RCCHK(h, h->af_out_coef.ensure((size_t)N * 11 * sizeof(double)), "staging");
-    RCCHK(h, h->af_out_aic.ensure((size_t)N * sizeof(double)), "staging");
-    RCCHK(h, h->af_out_status.ensure((size_t)N * sizeof(int32_t)), "staging");
-    RCCHK(h, h->af_out_nfits.ensure((size_t)N * sizeof(int32_t)), "staging");
-    if (T > 0) HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, (size_t)N * T * sizeof(double), hipMemcpyHostToDevice, s));
-    int rc = autofit_locked(h, h->h_series.as<double>(), N, T, T, max_p, max_d, max_q, h->af_out_order.as<int32_t>(),
-                            h->af_out_coef.as<double>(), h->af_out_aic.as<double>(), h->af_out_status.as<int32_t>(),
-                            h->af_out_nfits.as<int32_t>(), s, nullptr);
-    if (rc == ARIMA_OK) {
-        HIPCHK(h, hipMemcpyAsync(order_out, h->af_out_order.ptr, (size_t)N * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(coef_out, h->af_out_coef.ptr, (size_t)N * 11 * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(aic_out, h->af_out_aic.ptr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipMemcpyAsync(status_out, h->af_out_status.ptr, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        if (n_fits_out)
-            HIPCHK(h, hipMemcpyAsync(n_fits_out, h->af_out_nfits.ptr, (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    PASSCHK(f.begin());
+    const size_t ni = (size_t)N * sizeof(int32_t), nd = (size_t)N * sizeof(double);
+    PASSCHK(f.stage({stage_in(series, nd * T), stage_out(order_out, 4 * ni), stage_out(coef_out, 11 * nd),
+                     stage_out(aic_out, nd), stage_out(status_out, ni), stage_optional_out(n_fits_out, ni)}));
+    int rc = autofit_locked(h, f.dev<double>(0), N, T, T, max_p, max_d, max_q, f.dev<int32_t>(1), f.dev<double>(2),
+                            f.dev<double>(3), f.dev<int32_t>(4), f.dev<int32_t>(5), f.s(), nullptr);
+    rc = f.finish(rc);
     if (rc != ARIMA_OK) return rc;
     return take_fault(h);
 }
 
 int arima_kpss_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *stat_out, int32_t *status_out) {
     if (!h || N < 0 || T < 0) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N == 0) return ARIMA_OK;
     if (!series || !stat_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int32_t st = T <= 0 ? ARIMA_ST_NO_DATA : (T < 2 ? ARIMA_ST_NOT_ENOUGH_DATA : ARIMA_ST_OK);
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_ll.ensure((size_t)N * sizeof(double)), "staging");
+    PASSCHK(f.begin());
     if (st == ARIMA_ST_OK) {
         int64_t ld = 0;
-        RCCHK(h, upload_padded(h, series, N, T, &ld, s), "upload");
-        RCCHK(h, sts::launch_kpss_c(h->diff.as<double>(), ld, T, N, 0, nullptr, h->h_ll.as<double>(), s), "kpss");
-        HIPCHK(h, hipMemcpyAsync(stat_out, h->h_ll.ptr, (size_t)N * sizeof(double), hipMemcpyDeviceToHost, s));
+        RCCHK(h, upload_padded(h, series, N, T, &ld, f.s()), "upload");
+        PASSCHK(f.stage({stage_out(stat_out, (size_t)N * sizeof(double))}));
+        RCCHK(h, sts::launch_kpss_c(h->diff.as<double>(), ld, T, N, 0, nullptr, f.dev<double>(0), f.s()), "kpss");
     }
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
+    PASSCHK(f.finish());
     for (int64_t i = 0; i < N; ++i) {
         status_out[i] = st;
         if (st != ARIMA_ST_OK) stat_out[i] = NAN;
@@ -2345,39 +2300,18 @@ int arima_sample_batch_device(arima_handle *h, double *d_series, int64_t N, int3
                               int32_t d, int32_t q, int32_t I, const double *base_coef, double jitter,
                               uint64_t seed, int64_t first_series, void *stream) {
     if (!h || !base_coef || N < 0 || T < 0 || ld < T) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, sts::launch_sample(d_series, ld, N, T, p, d, q, I, base_coef, jitter, seed, first_series, s), "sample");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    PASSCHK(f.begin(stream));
+    RCCHK(h, sts::launch_sample(d_series, ld, N, T, p, d, q, I, base_coef, jitter, seed, first_series, f.s()),
+          "sample");
+    return f.finish();
 }
 
 // ---------------------------------------------------------------------------------------------------------
 // the small models: EWMA and GARCH(1,1) (arima_models.hip) -- fits, objective / gradient, the TimeSeriesModel pairs
 // ---------------------------------------------------------------------------------------------------------
 namespace {
-struct Span {
-    const void *p;
-    size_t bytes;
-};
-
-// no output may meet an input or another output
-int md_overlap(arima_handle *h, const Span *in, int n_in, const Span *out, int n_out) {
-    for (int a = 0; a < n_out; ++a) {
-        if (!out[a].p) continue;
-        for (int b = 0; b < n_in; ++b)
-            if (in[b].p && ::spans_meet(in[b].p, in[b].bytes, out[a].p, out[a].bytes))
-                return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
-        for (int b = a + 1; b < n_out; ++b)
-            if (out[b].p && ::spans_meet(out[a].p, out[a].bytes, out[b].p, out[b].bytes))
-                return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
-    }
-    return ARIMA_OK;
-}
-
 int md_fit_launch(arima_handle *h, int model, const double *rows, int64_t ld, int64_t N, int T, double *coef,
                   double *obj, int32_t *status, int32_t *n_eval, int32_t *n_grad, hipStream_t s) {
     RCCHK(h, h->md_ctl.ensure(sts::kModelCtlWords * sizeof(unsigned long long)), "counters");
@@ -2391,137 +2325,97 @@ int md_fit_launch(arima_handle *h, int model, const double *rows, int64_t ld, in
 int md_fit_host(arima_handle *h, int model, const double *series, int64_t N, int32_t T, double *coef_out,
                 double *obj_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!series || !coef_out || !obj_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
     const size_t row_bytes = (size_t)N * T * sizeof(double), nd = (size_t)N * sizeof(double),
                  ni = (size_t)N * sizeof(int32_t);
-    const Span in[1] = {{series, row_bytes}};
-    const Span out[5] = {{coef_out, nd * K}, {obj_out, nd}, {status_out, ni}, {n_eval_out, ni}, {n_grad_out, ni}};
-    RCCHK(h, md_overlap(h, in, 1, out, 5), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, h->h_coef.ensure(nd * K), "staging");
-    RCCHK(h, h->h_ll.ensure(nd), "staging");
-    RCCHK(h, h->h_status.ensure(ni), "staging");
-    RCCHK(h, h->h_neval.ensure(ni), "staging");
-    RCCHK(h, h->h_ngrad.ensure(ni), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, md_fit_launch(h, model, h->h_series.as<double>(), T, N, T, h->h_coef.as<double>(), h->h_ll.as<double>(),
-                           h->h_status.as<int32_t>(), h->h_neval.as<int32_t>(), h->h_ngrad.as<int32_t>(), s), "fit");
-    HIPCHK(h, hipMemcpyAsync(coef_out, h->h_coef.ptr, nd * K, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(obj_out, h->h_ll.ptr, nd, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipMemcpyAsync(status_out, h->h_status.ptr, ni, hipMemcpyDeviceToHost, s));
-    if (n_eval_out) HIPCHK(h, hipMemcpyAsync(n_eval_out, h->h_neval.ptr, ni, hipMemcpyDeviceToHost, s));
-    if (n_grad_out) HIPCHK(h, hipMemcpyAsync(n_grad_out, h->h_ngrad.ptr, ni, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, check_overlap(h, {ByteSpan(series, row_bytes)},
+                           {ByteSpan(coef_out, nd * K), ByteSpan(obj_out, nd), ByteSpan(status_out, ni),
+                            ByteSpan(n_eval_out, ni), ByteSpan(n_grad_out, ni)}), "overlap");
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_out(coef_out, nd * K), stage_out(obj_out, nd),
+                     stage_out(status_out, ni), stage_optional_out(n_eval_out, ni),
+                     stage_optional_out(n_grad_out, ni)}));
+    RCCHK(h, md_fit_launch(h, model, f.dev<double>(0), T, N, T, f.dev<double>(1), f.dev<double>(2), f.dev<int32_t>(3),
+                           f.dev<int32_t>(4), f.dev<int32_t>(5), f.s()), "fit");
+    return f.finish();
 }
 
 int md_fit_device(arima_handle *h, int model, const double *d_series, int64_t N, int32_t T, int64_t ld,
                   double *d_coef_out, double *d_obj_out, int32_t *d_status_out, int32_t *d_n_eval_out,
                   int32_t *d_n_grad_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     if (N < 0 || T < 1 || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!d_series || !d_coef_out || !d_obj_out || !d_status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
     const size_t nd = (size_t)N * sizeof(double), ni = (size_t)N * sizeof(int32_t);
-    const Span in[1] = {{d_series, ((size_t)(N - 1) * ld + T) * sizeof(double)}};
-    const Span out[5] = {{d_coef_out, nd * K}, {d_obj_out, nd}, {d_status_out, ni}, {d_n_eval_out, ni},
-                         {d_n_grad_out, ni}};
-    RCCHK(h, md_overlap(h, in, 1, out, 5), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
+    RCCHK(h, check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double))},
+                           {ByteSpan(d_coef_out, nd * K), ByteSpan(d_obj_out, nd), ByteSpan(d_status_out, ni),
+                            ByteSpan(d_n_eval_out, ni), ByteSpan(d_n_grad_out, ni)}), "overlap");
+    PASSCHK(f.begin(stream));
     RCCHK(h, md_fit_launch(h, model, d_series, ld, N, T, d_coef_out, d_obj_out, d_status_out, d_n_eval_out,
-                           d_n_grad_out, s), "fit");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+                           d_n_grad_out, f.s()), "fit");
+    return f.finish();
 }
 
 // objective (want_grad == 0: out N) or gradient (out N x K) at params (N x K), host buffers
 int md_eval_host(arima_handle *h, int model, const double *series, int64_t N, int32_t T, const double *params,
                  double *out, int want_grad) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
     if (!series || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
     const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
     const size_t out_bytes = (size_t)N * (want_grad ? K : 1) * sizeof(double);
-    const Span in[2] = {{series, row_bytes}, {params, par_bytes}};
-    const Span o[1] = {{out, out_bytes}};
-    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, h->h_coef.ensure(par_bytes), "staging");
-    RCCHK(h, h->h_aux.ensure(out_bytes), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, series, row_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, params, par_bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_model_eval(model, h->h_series.as<double>(), T, N, T, h->h_coef.as<double>(),
-                                    want_grad ? nullptr : h->h_aux.as<double>(),
-                                    want_grad ? h->h_aux.as<double>() : nullptr, s), "model eval");
-    HIPCHK(h, hipMemcpyAsync(out, h->h_aux.ptr, out_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(params, par_bytes)}, {ByteSpan(out, out_bytes)}),
+          "overlap");
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(params, par_bytes), stage_out(out, out_bytes)}));
+    RCCHK(h, sts::launch_model_eval(model, f.dev<double>(0), T, N, T, f.dev<double>(1),
+                                    want_grad ? nullptr : f.dev<double>(2), want_grad ? f.dev<double>(2) : nullptr,
+                                    f.s()), "model eval");
+    return f.finish();
 }
 
 int md_effects_host(arima_handle *h, int model, const double *in_rows, int64_t N, int32_t T, const double *params,
                     double *out, int add) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0 || T == 0) return ARIMA_OK;
     if (!in_rows || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
     const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
-    const Span in[2] = {{in_rows, row_bytes}, {params, par_bytes}};
-    const Span o[1] = {{out, row_bytes}};
-    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = h->stream;
-    begin_call(h, s);
-    RCCHK(h, h->h_series.ensure(row_bytes), "staging");
-    RCCHK(h, h->md_out.ensure(row_bytes), "staging");
-    RCCHK(h, h->h_coef.ensure(par_bytes), "staging");
-    HIPCHK(h, hipMemcpyAsync(h->h_series.ptr, in_rows, row_bytes, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->h_coef.ptr, params, par_bytes, hipMemcpyHostToDevice, s));
-    RCCHK(h, sts::launch_model_effects(model, h->h_series.as<double>(), T, h->h_coef.as<double>(),
-                                       h->md_out.as<double>(), T, N, T, add, s), "model effects");
-    HIPCHK(h, hipMemcpyAsync(out, h->md_out.ptr, row_bytes, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, end_call(h, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    return ARIMA_OK;
+    RCCHK(h, check_overlap(h, {ByteSpan(in_rows, row_bytes), ByteSpan(params, par_bytes)}, {ByteSpan(out, row_bytes)}),
+          "overlap");
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(in_rows, row_bytes), stage_in(params, par_bytes), stage_out(out, row_bytes)}));
+    RCCHK(h, sts::launch_model_effects(model, f.dev<double>(0), T, f.dev<double>(1), f.dev<double>(2), T, N, T, add,
+                                       f.s()), "model effects");
+    return f.finish();
 }
 
 int md_effects_device(arima_handle *h, int model, const double *d_in, int64_t N, int32_t T, int64_t ld,
                       const double *d_params, double *d_out, int64_t ld_out, void *stream, int add) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    std::lock_guard<std::mutex> lk(h->mu);
+    CallFrame f(h, kDeviceBuffers);
     if (N < 0 || T < 0 || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0 || T == 0) return ARIMA_OK;
     if (!d_in || !d_params || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
-    const Span in[2] = {{d_in, ((size_t)(N - 1) * ld + T) * sizeof(double)}, {d_params, (size_t)N * K * sizeof(double)}};
-    const Span o[1] = {{d_out, ((size_t)(N - 1) * ld_out + T) * sizeof(double)}};
-    RCCHK(h, md_overlap(h, in, 2, o, 1), "overlap");
-    HIPCHK(h, hipSetDevice(h->device));
-    hipStream_t s = stream ? (hipStream_t)stream : h->stream;
-    begin_call(h, s);
-    RCCHK(h, sts::launch_model_effects(model, d_in, ld, d_params, d_out, ld_out, N, T, add, s), "model effects");
-    HIPCHK(h, end_call(h, s));
-    return ARIMA_OK;
+    RCCHK(h, check_overlap(h, {ByteSpan(d_in, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
+                               ByteSpan(d_params, N * K * (int64_t)sizeof(double))},
+                           {ByteSpan(d_out, ((N - 1) * ld_out + T) * (int64_t)sizeof(double))}), "overlap");
+    PASSCHK(f.begin(stream));
+    RCCHK(h, sts::launch_model_effects(model, d_in, ld, d_params, d_out, ld_out, N, T, add, f.s()), "model effects");
+    return f.finish();
 }
 }  // namespace
 

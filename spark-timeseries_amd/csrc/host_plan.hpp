@@ -1,7 +1,8 @@
 // host_plan.hpp — the host-side sizing arithmetic of arima_runtime.cpp as pure functions: the host path's chunk
-// schedule, the layout of one chunk's results in pinned staging, the partition par_memcpy hands its threads, and the
-// rows per slice of the sliced device fit and of the residual diagnostics. No HIP headers: a CPU program includes this
-// file and sweeps the functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of the formulas.
+// schedule, the layout of one chunk's results in pinned staging, the layout of a host-buffer call's staged arrays, the
+// byte-span overlap rule of the entry points, the partition par_memcpy hands its threads, and the rows per slice of the
+// sliced device fit and of the residual diagnostics. No HIP headers: a CPU program includes this file and sweeps the
+// functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of the formulas.
 #pragma once
 
 #include <algorithm>
@@ -57,6 +58,41 @@ inline size_t pin_layout(int64_t n, int k, size_t off[6]) {
     off[4] = o; o += round_up(n * 4, 256);
     off[5] = o; o += round_up(n, 256);
     return o;
+}
+
+// The staged arrays of one host-buffer call in one device block (the same idea as pin_layout, for any set of arrays):
+// region i of bytes[i] bytes starts at off[i], a multiple of 256, in declaration order; a zero-byte region takes no
+// space. Returns the block's size.
+inline size_t arena_layout(const size_t *bytes, int n, size_t *off) {
+    size_t o = 0;
+    for (int i = 0; i < n; ++i) {
+        off[i] = o;
+        o += (bytes[i] + 255) / 256 * 256;
+    }
+    return o;
+}
+
+// A caller's buffer as a byte range. A null pointer or a non-positive size makes it empty, and an empty span meets
+// nothing.
+struct ByteSpan {
+    uintptr_t lo = 0, hi = 0;
+    ByteSpan() = default;
+    ByteSpan(const void *p, int64_t bytes)
+        : lo((uintptr_t)p), hi(p && bytes > 0 ? (uintptr_t)p + (uintptr_t)bytes : (uintptr_t)p) {}
+    bool empty() const { return lo >= hi; }
+    bool meets(const ByteSpan &o) const { return !empty() && !o.empty() && lo < o.hi && o.lo < hi; }
+};
+
+// The rule of every entry point that checks its buffers: no output meets an input, no two outputs meet.
+enum Overlap { kDisjoint = 0, kOutputMeetsInput, kOutputsMeet };
+inline Overlap find_overlap(const ByteSpan *in, int n_in, const ByteSpan *out, int n_out) {
+    for (int a = 0; a < n_out; ++a) {
+        for (int b = 0; b < n_in; ++b)
+            if (out[a].meets(in[b])) return kOutputMeetsInput;
+        for (int b = a + 1; b < n_out; ++b)
+            if (out[a].meets(out[b])) return kOutputsMeet;
+    }
+    return kDisjoint;
 }
 
 // The (offset, length) pieces par_memcpy copies, one per thread: at most `threads` of them, none below 4 MiB unless

@@ -1,6 +1,7 @@
 // Sweeps the host-side planners of spark-timeseries_amd/csrc/host_plan.hpp (what arima_runtime.cpp sizes its device and
 // pinned buffers with) on the CPU: the host path's chunk schedule against the properties every plan must have and
-// against the schedule it replaced, the pinned-staging layout, par_memcpy and its partition, and the slice formulas.
+// against the schedule it replaced, the pinned-staging layout, the staging-arena layout, the byte-span overlap rule
+// against a per-byte test and against the two tests it replaced, par_memcpy and its partition, and the slice formulas.
 // Exits non-zero at the first offending tuple. Built plain and under AddressSanitizer + UBSan (hostplan.mk).
 #include <cinttypes>
 #include <cstdio>
@@ -168,6 +169,116 @@ static void sweep_pin_layout() {
     std::printf("pin_layout: aligned, disjoint, inside the size, monotone in n\n");
 }
 
+static void check_arena(const size_t *bytes, int n) {
+    size_t off[8] = {}, end = 0;
+    const size_t total = P::arena_layout(bytes, n, off);
+    for (int i = 0; i < n; ++i) {
+        if (off[i] % 256) FAIL("arena_layout: offset %d = %zu of %d regions not 256-byte aligned", i, off[i], n);
+        if (off[i] < end) FAIL("arena_layout: region %d at %zu starts before the end %zu of the regions declared before it", i, off[i], end);
+        if (bytes[i] == 0 && off[i] != (end + 255) / 256 * 256) FAIL("arena_layout: empty region %d at %zu takes space", i, off[i]);
+        end = off[i] + bytes[i];
+    }
+    if (total != (end + 255) / 256 * 256) FAIL("arena_layout: size %zu of %d regions, last one ends at %zu", total, n, end);
+    // without its empty regions the layout is the same
+    size_t dense[8], doff[8];
+    int m = 0;
+    for (int i = 0; i < n; ++i)
+        if (bytes[i]) dense[m++] = bytes[i];
+    if (P::arena_layout(dense, m, doff) != total) FAIL("arena_layout: empty regions change the size of %d regions", n);
+    for (int i = 0, j = 0; i < n; ++i)
+        if (bytes[i] && doff[j++] != off[i]) FAIL("arena_layout: empty regions move region %d of %d", i, n);
+}
+
+static void sweep_arena_layout() {
+    const size_t pick[8] = {0, 1, 7, 8, 255, 256, 257, 4096 + 8};
+    size_t bytes[8];
+    int64_t cases = 0;
+    for (int n = 0; n <= 8; ++n) {               // every tuple of every count: 8^0 + ... + 8^8
+        int64_t tuples = 1;
+        for (int i = 0; i < n; ++i) tuples *= 8;
+        for (int64_t t = 0; t < tuples; ++t, ++cases) {
+            int64_t v = t;
+            for (int i = 0; i < n; ++i, v /= 8) bytes[i] = pick[v % 8];
+            check_arena(bytes, n);
+        }
+    }
+    std::printf("arena_layout: all %" PRId64 " tuples of 0..8 regions aligned, disjoint, in order, empty regions free\n", cases);
+}
+
+// The two overlap tests ByteSpan::meets replaced in arima_runtime.cpp, kept here as the reference: the fit pipeline's
+// [lo, hi) pairs (with the function that filled them) and the entry points' (pointer, bytes) form.
+static void old_set_span(uintptr_t (&sp)[2], const void *p, int64_t bytes) {
+    sp[0] = (uintptr_t)p;
+    sp[1] = p && bytes > 0 ? (uintptr_t)p + (uintptr_t)bytes : (uintptr_t)p;
+}
+static bool old_spans_meet(const uintptr_t (&a)[2], const uintptr_t (&b)[2]) {
+    return a[0] < a[1] && b[0] < b[1] && a[0] < b[1] && b[0] < a[1];
+}
+static bool old_spans_meet(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a_bytes > 0 && b_bytes > 0 && a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+static bool bytes_shared(int s1, int l1, int s2, int l2) {
+    for (int x = s1; x < s1 + l1; ++x)
+        if (x >= s2 && x < s2 + l2) return true;
+    return false;
+}
+
+static void sweep_spans() {
+    static unsigned char arr[64 + 16];           // starts 0..63 of the first 64 bytes, lengths 0..16
+    int64_t pairs = 0;
+    for (int s1 = 0; s1 < 64; ++s1)
+        for (int l1 = 0; l1 <= 16; ++l1)
+            for (int s2 = 0; s2 < 64; ++s2)
+                for (int l2 = 0; l2 <= 16; ++l2, ++pairs) {
+                    const P::ByteSpan a(arr + s1, l1), b(arr + s2, l2);
+                    const bool want = bytes_shared(s1, l1, s2, l2);
+                    if (a.meets(b) != want || b.meets(a) != want) FAIL("meets: [%d, +%d) and [%d, +%d): expected %d", s1, l1, s2, l2, (int)want);
+                    uintptr_t oa[2], ob[2];
+                    old_set_span(oa, arr + s1, l1);
+                    old_set_span(ob, arr + s2, l2);
+                    if (old_spans_meet(oa, ob) != want || old_spans_meet(arr + s1, (size_t)l1, arr + s2, (size_t)l2) != want)
+                        FAIL("the replaced overlap tests disagree at [%d, +%d) and [%d, +%d)", s1, l1, s2, l2);
+                }
+    // null and empty spans meet nothing, each other and themselves included
+    for (int s = 0; s < 64; ++s)
+        for (int l = 0; l <= 16; ++l) {
+            const P::ByteSpan x(arr + s, l), null_sized(nullptr, 16), null_empty(nullptr, 0), negative(arr + s, -8), empty(arr + s, 0);
+            for (const P::ByteSpan &e : {null_sized, null_empty, negative, empty})
+                if (!e.empty() || e.meets(x) || x.meets(e) || e.meets(e)) FAIL("an empty span meets [%d, +%d)", s, l);
+        }
+    // the in/out rule on seeded draws of up to 2 inputs and 6 outputs (the most an entry point or a fit call has)
+    std::mt19937_64 rng(20261021);
+    int64_t refused = 0, draws = 300000;
+    for (int64_t t = 0; t < draws; ++t) {
+        struct R { int s, l; bool null; } in[2], out[6];
+        P::ByteSpan is[2], os[6];
+        const int n_in = (int)(rng() % 3), n_out = (int)(rng() % 7);
+        auto draw = [&](R &r, P::ByteSpan &sp) {
+            r = {(int)(rng() % 64), (int)(rng() % 17), rng() % 8 == 0};
+            if (rng() % 4 == 0) r.l = (int)(rng() % 3);              // more short and empty ranges
+            sp = P::ByteSpan(r.null ? nullptr : arr + r.s, r.l);
+            if (r.null) r.l = 0;
+        };
+        for (int i = 0; i < n_in; ++i) draw(in[i], is[i]);
+        for (int i = 0; i < n_out; ++i) draw(out[i], os[i]);
+        bool out_in = false, out_out = false;
+        for (int a = 0; a < n_out; ++a) {
+            for (int b = 0; b < n_in; ++b) out_in |= bytes_shared(out[a].s, out[a].l, in[b].s, in[b].l);
+            for (int b = a + 1; b < n_out; ++b) out_out |= bytes_shared(out[a].s, out[a].l, out[b].s, out[b].l);
+        }
+        const P::Overlap got = P::find_overlap(is, n_in, os, n_out);
+        if ((got != P::kDisjoint) != (out_in || out_out)) FAIL("find_overlap: draw %" PRId64 " refused %d, bytes shared %d", t, (int)got, (int)(out_in || out_out));
+        if ((got == P::kOutputMeetsInput && !out_in) || (got == P::kOutputsMeet && !out_out))
+            FAIL("find_overlap: draw %" PRId64 " names violation %d, which the bytes do not show", t, (int)got);
+        refused += got != P::kDisjoint;
+    }
+    if (refused == 0 || refused == draws) FAIL("find_overlap: the draws are all alike (%" PRId64 " refused)", refused);
+    std::printf("byte spans: %" PRId64 " pairs equal the per-byte test and both replaced tests; in/out rule on %" PRId64
+                " draws (%" PRId64 " refused)\n", pairs, draws, refused);
+}
+
 static void sweep_memcpy() {
     const size_t MiB = size_t(1) << 20;
     const size_t sizes_b[] = {0, 1, 63, 64, 65, 4 * MiB - 1, 4 * MiB, 8 * MiB, 8 * MiB + 1, 37 * MiB + 13};
@@ -228,6 +339,8 @@ static void sweep_slices() {
 int main() {
     sweep_chunks();
     sweep_pin_layout();
+    sweep_arena_layout();
+    sweep_spans();
     sweep_memcpy();
     sweep_slices();
     std::printf("hostplan OK\n");
