@@ -181,6 +181,42 @@ def test_kpss_r_equivalence():
     assert O.kpss([1.0], "c")[0] == 5 and O.kpss([], "c")[0] == 6
 
 
+def _kpss_long_double(row):
+    """kpsstest(ts, "c") by its formula (TimeSeriesStatisticalTests.scala:369-431) in long double, not by the
+    reference's steps: residuals about the mean, the sum of the squared cumulative sums, the Bartlett-weighted
+    autocovariances up to (3 sqrt(n) / 13).toInt, and n * n as a float (no Int product)."""
+    y = np.asarray(row, dtype=np.longdouble)
+    n = len(y)
+    e = y - y.sum() / n
+    s2 = (np.cumsum(e) ** 2).sum()
+    lag = int(3 * np.sqrt(n) / 13)
+    terms = np.longdouble(0)
+    for i in range(1, lag + 1):
+        terms += (e[i:] * e[:-i]).sum() * (1 - np.longdouble(i) / (lag + 1))
+    long_run_variance = 2 * terms / n + (e * e).sum() / n
+    return s2 / long_run_variance / (np.longdouble(n) * n)
+
+
+# The restatement's worst relative difference from the long-double formula over the rows below is 1.53e-11 (T = 2, a
+# random walk * 1e3 + 1e6: the mean's rounding against residuals of ~1e3; 1.4e-12 at most from T = 3 on). The bound is
+# ten times that: room for another libm or long-double format, while a wrong lag or Bartlett weight moves the statistic
+# by parts in a hundred.
+KPSS_FORMULA_RTOL = 1.53e-10
+
+
+@pytest.mark.parametrize("T", [2, 3, 18, 19, 75, 76, 300, 1024, 4096, 20448, 20449, 46340])
+def test_kpss_matches_long_double_formula(T):
+    rng = np.random.default_rng(7000 + T)
+    rows = np.concatenate([rng.standard_normal((2, T)), np.cumsum(rng.standard_normal((2, T)), axis=1),
+                           np.cumsum(rng.standard_normal((2, T)), axis=1) * 1e3 + 1e6])
+    for i, row in enumerate(rows):
+        st, stat = O.kpss(row, "c")
+        ref = _kpss_long_double(row)
+        assert st == 0 and np.isfinite(ref)
+        rel = float(abs(stat - ref) / abs(ref))
+        assert rel <= KPSS_FORMULA_RTOL, (T, i, stat, float(ref), rel)
+
+
 def _autofit_kat_series():
     # ARIMASuite.scala:181-185: ARIMAModel(2, 0, 0, [2.5, 0.4, 0.3], true).sample(250, new MersenneTwister(10L))
     sampled = O.add_time_dependent_effects(mt_gauss(10, 250), 2, 0, 0, 1, [2.5, 0.4, 0.3])
