@@ -38,12 +38,12 @@ int launch_bobyqa_refit_list(const int64_t *off, int ncombos, int64_t total, con
 
 int launch_bobyqa_refit_dim(int k, const double *rows_, int64_t ld, int n, const int32_t *lists, int64_t N,
                             const int64_t *off, int ncombos, int kc, const int32_t *list, const unsigned *counts,
-                            int64_t rows, const double *init, const int32_t *init_status, double *coef, double *ll,
-                            int32_t *status, uint8_t *flags, bool wave, hipStream_t s) {
+                            int64_t rows, const double *init, const int32_t *init_status, const FitOut &o, bool wave,
+                            hipStream_t s) {
 #define BQ_REFIT(K)                                                                                                   \
     case K:                                                                                                           \
         return launch_bobyqa_refit_k<K>(rows_, ld, n, lists, N, off, ncombos, kc, list, counts, rows, init,           \
-                                        init_status, coef, ll, status, flags, wave, s);
+                                        init_status, o.coef, o.ll, o.status, o.flags, wave, s);
     switch (k) {
         BQ_REFIT(2) BQ_REFIT(3) BQ_REFIT(4) BQ_REFIT(5) BQ_REFIT(6) BQ_REFIT(7) BQ_REFIT(8) BQ_REFIT(9) BQ_REFIT(10)
         BQ_REFIT(11)
@@ -54,16 +54,15 @@ int launch_bobyqa_refit_dim(int k, const double *rows_, int64_t ld, int n, const
 }
 
 int launch_bobyqa_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, const double *init,
-                      const int32_t *init_status, const int32_t *refit_status, double *coef_out, double *ll_out,
-                      int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, bool wave,
+                      const int32_t *init_status, const int32_t *refit_status, const FitOut &o, bool wave,
                       hipStream_t s) {
     if (N == 0) return ARIMA_OK;
     if (!gen_orders_ok(p, q) || I + p + q > BQ_KMAX) return ARIMA_E_UNSUPPORTED;
     // one instantiation per dimension k = I + p + q: Powell's loops get compile-time bounds
 #define BQ_LAUNCH(K)                                                                                                  \
     case K:                                                                                                           \
-        return launch_bobyqa_fit_k<K>(y, ld, n, N, p, q, I, init, init_status, refit_status, coef_out, ll_out,        \
-                                      status_out, n_eval_out, n_grad_out, flags_out, wave, s);
+        return launch_bobyqa_fit_k<K>(y, ld, n, N, p, q, I, init, init_status, refit_status, o.coef, o.ll,            \
+                                      o.status, o.n_eval, o.n_grad, o.flags, wave, s);
     switch (I + p + q) {
         BQ_LAUNCH(0) BQ_LAUNCH(1) BQ_LAUNCH(2) BQ_LAUNCH(3) BQ_LAUNCH(4) BQ_LAUNCH(5) BQ_LAUNCH(6) BQ_LAUNCH(7)
         BQ_LAUNCH(8) BQ_LAUNCH(9) BQ_LAUNCH(10) BQ_LAUNCH(11)

@@ -528,27 +528,24 @@ int launch_gen_hr_init(const double *y, int64_t ld, int n, int64_t N, int p, int
     return ARIMA_OK;
 }
 
-int launch_gen_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, double *coef_out, double *ll_out,
-                      int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, int dd,
+int launch_gen_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, const FitOut &o, int dd,
                       hipStream_t s) {
     if (!gen_orders_ok(p, 0)) return ARIMA_E_UNSUPPORTED;
     if (N == 0) return ARIMA_OK;
     const unsigned grid = std::min(gen_grid(N, 64), kGenGridMax);
-    hipLaunchKernelGGL(k_gen_ar_fit, dim3(grid), dim3(64), 0, s, y, ld, n, N, p, I, coef_out, ll_out, status_out,
-                       n_eval_out, n_grad_out, flags_out, dd);
+    hipLaunchKernelGGL(k_gen_ar_fit, dim3(grid), dim3(64), 0, s, y, ld, n, N, p, I, o.coef, o.ll, o.status, o.n_eval,
+                       o.n_grad, o.flags, dd);
     STS_GEN_CHECK();
     return ARIMA_OK;
 }
 
 int launch_gen_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear, const double *init,
-                   const int32_t *init_status, double *coef_out, double *ll_out, int32_t *status_out,
-                   int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, unsigned long long *ctl, int dd,
-                   hipStream_t s) {
+                   const int32_t *init_status, const FitOut &o, unsigned long long *ctl, int dd, hipStream_t s) {
     if (!gen_orders_ok(p, q)) return ARIMA_E_UNSUPPORTED;
     if (N == 0) return ARIMA_OK;
     const unsigned grid = std::min(gen_grid(N, 64), kGenGridMax);
-    hipLaunchKernelGGL(k_gen_fit, dim3(grid), dim3(64), 0, s, y, ld, n, N, p, q, I, smear, init, init_status, coef_out,
-                       ll_out, status_out, n_eval_out, n_grad_out, flags_out, ctl, dd);
+    hipLaunchKernelGGL(k_gen_fit, dim3(grid), dim3(64), 0, s, y, ld, n, N, p, q, I, smear, init, init_status, o.coef,
+                       o.ll, o.status, o.n_eval, o.n_grad, o.flags, ctl, dd);
     STS_GEN_CHECK();
     return ARIMA_OK;
 }

@@ -606,27 +606,23 @@ int launch_hr_init(const double *y, int64_t ld, int n, int64_t N, int p, int q, 
 #undef C_
 }
 
-int launch_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, double *coef_out, double *ll_out,
-                  int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out,
-                  hipStream_t s, int dd) {
+int launch_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, const FitOut &o, hipStream_t s,
+                  int dd) {
     if (N == 0) return ARIMA_OK;
-    if (gen_order(p, 0))
-        return launch_gen_ar_fit(y, ld, n, N, p, I, coef_out, ll_out, status_out, n_eval_out, n_grad_out, flags_out, dd,
-                                 s);
-#define C_(PP) launch_ar_fit_P<PP>(y, ld, n, N, I, coef_out, ll_out, status_out, n_eval_out, n_grad_out, flags_out, s, dd)
+    if (gen_order(p, 0)) return launch_gen_ar_fit(y, ld, n, N, p, I, o, dd, s);
+    // (the order-templated launchers and the kernels keep their own parameter lists)
+#define C_(PP) launch_ar_fit_P<PP>(y, ld, n, N, I, o.coef, o.ll, o.status, o.n_eval, o.n_grad, o.flags, s, dd)
     STS_P_SWITCH(C_)
 #undef C_
 }
 
-int launch_cg_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear,
-                  const double *init, const int32_t *init_status, double *coef_out, double *ll_out,
-                  int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out,
-                  unsigned long long *ctl, int grid_blocks, int express_blocks, unsigned char *xq, unsigned *xready,
-                  int join_express, hipStream_t s, int dd) {
+int launch_cg_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear, const double *init,
+                  const int32_t *init_status, const FitOut &o, unsigned long long *ctl, int grid_blocks,
+                  int express_blocks, unsigned char *xq, unsigned *xready, int join_express, hipStream_t s, int dd) {
     if (N == 0) return ARIMA_OK;
 #define C_(PP)                                                                                             \
-    launch_cg_fit_P<PP>(y, ld, n, N, q, I, smear, init, init_status, coef_out, ll_out, status_out, n_eval_out, \
-                        n_grad_out, flags_out, ctl, grid_blocks, express_blocks, xq, xready, join_express, s, dd)
+    launch_cg_fit_P<PP>(y, ld, n, N, q, I, smear, init, init_status, o.coef, o.ll, o.status, o.n_eval,     \
+                        o.n_grad, o.flags, ctl, grid_blocks, express_blocks, xq, xready, join_express, s, dd)
     STS_P_SWITCH(C_)
 #undef C_
 }

@@ -66,14 +66,20 @@ int launch_fit_prep(const FitPrep &prep, hipStream_t s);
 // fly (arima_device.hpp stream_row); 0 = y holds the differenced rows.
 int launch_hr_init(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, double *init_out,
                    int32_t *status_out, hipStream_t s, int hr_grid = 0, int dd = 0, const FitPrep &prep = FitPrep{});
-int launch_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, double *coef_out, double *ll_out,
-                  int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out,
-                  hipStream_t s, int dd = 0);
-int launch_cg_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear,
-                  const double *init, const int32_t *init_status, double *coef_out, double *ll_out,
-                  int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out,
-                  unsigned long long *ctl, int grid_blocks, int express_blocks, unsigned char *xq, unsigned *xready,
-                  int join_express, hipStream_t s, int dd = 0);
+// The per-series outputs of a fit: coef is N x k, the others N; n_eval, n_grad and flags are optional (null).
+// at(first, k): the bundle `first` rows further on (coefficient rows of k doubles); null members stay null
+struct FitOut {
+    double *coef, *ll; int32_t *status, *n_eval, *n_grad; uint8_t *flags;
+    FitOut at(int64_t f, int k) const {
+        return {coef ? coef + f * k : nullptr, ll ? ll + f : nullptr,         status ? status + f : nullptr,
+                n_eval ? n_eval + f : nullptr, n_grad ? n_grad + f : nullptr, flags ? flags + f : nullptr};
+    }
+};
+int launch_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, const FitOut &out, hipStream_t s,
+                  int dd = 0);
+int launch_cg_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear, const double *init,
+                  const int32_t *init_status, const FitOut &out, unsigned long long *ctl, int grid_blocks,
+                  int express_blocks, unsigned char *xq, unsigned *xready, int join_express, hipStream_t s, int dd = 0);
 constexpr int kExpressRingEntries = 32768;      // k_cg_fit's express hand-offs per launch (entries never reused)
 constexpr int kExpressRingBytes = kExpressRingEntries * 512;   // x kExpressEntryBytes
 constexpr int kExpressReadyBytes = kExpressRingEntries * 4;
@@ -131,8 +137,7 @@ int launch_af_finish(int64_t N, const AfSeries *st, const double *best_coef, int
 // css-bobyqa (arima_bobyqa.hip): one lane per series after the initial parameters; refit_status (optional): only the
 // series whose css-cgd status there is an optimizer exception (autoFit's fitTryBothStrategies) are refitted in place
 int launch_bobyqa_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, const double *init,
-                      const int32_t *init_status, const int32_t *refit_status, double *coef_out, double *ll_out,
-                      int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, bool wave,
+                      const int32_t *init_status, const int32_t *refit_status, const FitOut &out, bool wave,
                       hipStream_t s);
 
 // autoFit: the css-bobyqa retries of a whole round (every order's rows whose css-cgd fit threw in the optimizer), one
@@ -146,8 +151,8 @@ int launch_bobyqa_refit_list(const int64_t *off, int ncombos, int64_t total, con
                              int64_t stride, unsigned *counts, hipStream_t s);
 int launch_bobyqa_refit_dim(int k, const double *rows_, int64_t ld, int n, const int32_t *lists, int64_t N,
                             const int64_t *off, int ncombos, int kc, const int32_t *list, const unsigned *counts,
-                            int64_t rows, const double *init, const int32_t *init_status, double *coef, double *ll,
-                            int32_t *status, uint8_t *flags, bool wave, hipStream_t s);
+                            int64_t rows, const double *init, const int32_t *init_status, const FitOut &out, bool wave,
+                            hipStream_t s);
 
 int hr_shape_status_host(int n, int p, int q, int I);
 int ar_shape_status_host(int n, int p, int I);
@@ -164,13 +169,10 @@ inline bool fuse_pays(int p, int q) { return gen_order(p, q) || p + q <= 6; }
 bool gen_orders_ok(int p, int q);
 int launch_gen_hr_init(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, double *init_out,
                        int32_t *status_out, int dd, const FitPrep &prep, hipStream_t s);
-int launch_gen_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, double *coef_out, double *ll_out,
-                      int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, int dd,
+int launch_gen_ar_fit(const double *y, int64_t ld, int n, int64_t N, int p, int I, const FitOut &out, int dd,
                       hipStream_t s);
 int launch_gen_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear, const double *init,
-                   const int32_t *init_status, double *coef_out, double *ll_out, int32_t *status_out,
-                   int32_t *n_eval_out, int32_t *n_grad_out, uint8_t *flags_out, unsigned long long *ctl, int dd,
-                   hipStream_t s);
+                   const int32_t *init_status, const FitOut &out, unsigned long long *ctl, int dd, hipStream_t s);
 int launch_gen_css_loglik(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, const double *coef,
                           double *ll_out, hipStream_t s);
 int launch_gen_css_grad(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int smear,

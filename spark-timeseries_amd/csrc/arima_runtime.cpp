@@ -21,6 +21,7 @@
 
 #include "../../include/sparkts_arima.h"
 #include "arima_launch.hpp"
+#include "fit_stats.hpp"
 #include "host_plan.hpp"
 
 namespace {
@@ -52,22 +53,51 @@ struct DevBuf {
 };
 
 constexpr int kNumEvents = 5;
-constexpr int kCtlWords = sts::kFitCtlWords;   // device counters of the fit kernel (k_cg_fit's ctl[]; ctl[32] = series written)
+using namespace sts::stats;                    // kCtlWords and the names of the fit kernel's counter words
+static_assert(kCtlWords == sts::kFitCtlWords, "fit_stats.hpp names the words the launchers prepare");
+using sts::FitOut;
 
-// What arima_get_last_stats needs to turn the device counters of the last fit into arima_fit_stats. The fit
-// entry points do not wait for the device (the `*_device` contract): the counters are copied to pinned host
-// memory in stream order and the stats are computed when they are asked for.
-struct PendingStats {
-    bool valid = false;
-    int64_t N = 0;
-    int n = 0, p = 0, q = 0, I = 0;
-    bool ar_only = false, user_init = false, cg = false;
-    int64_t grid = 0, express = 0;
+// What arima_get_last_stats needs to turn the device counters of one fit (or slice, or host chunk) into
+// arima_fit_stats. The fit entry points do not wait for the device (the `*_device` contract): the counters are copied
+// to pinned host memory in stream order and the stats are computed when they are asked for (fit_stats.hpp).
+struct FitRecord {
+    hipEvent_t ev[kNumEvents] = {};           // start, after differencing, init, fit; (slots) after the counter copy
+    unsigned long long *ctl_host = nullptr;   // pinned, kCtlWords
+    FitShape ps;
+    int create() {
+        for (auto &e : ev)
+            if (!e && hipEventCreate(&e) != hipSuccess) return ARIMA_E_DEVICE;
+        return ARIMA_OK;
+    }
+    void destroy() {
+        for (auto &e : ev)
+            if (e) hipEventDestroy(e);
+    }
+    // the record's stats once its last event has passed; it stays valid (the callers retire it)
+    arima_fit_stats stats() const {
+        if (!ps.valid) return arima_fit_stats{};
+        float d = 0, i = 0, f = 0, t = 0;
+        hipEventElapsedTime(&d, ev[0], ev[1]);
+        hipEventElapsedTime(&i, ev[1], ev[2]);
+        hipEventElapsedTime(&f, ev[2], ev[3]);
+        hipEventElapsedTime(&t, ev[0], ev[3]);
+        return fit_stats(ps, ctl_host, FitTimes{d, i, f, t});
+    }
 };
 
 // Device workspace of one fit in flight: Hannan-Rissanen init, the fit kernel's counters and its express ring.
 struct FitWs {
     DevBuf init, hr_status, ctl, xring, xready;
+    // every workspace of a fit of N series with k parameters, before the first launch (a growing DevBuf frees, and
+    // hipFree synchronises the device)
+    int reserve(int64_t N, int k) {
+        int rc = init.ensure((size_t)N * std::max(k, 1) * sizeof(double));
+        if (rc == ARIMA_OK) rc = hr_status.ensure((size_t)N * sizeof(int32_t));
+        if (rc == ARIMA_OK) rc = ctl.ensure(kCtlWords * sizeof(unsigned long long));
+        if (rc == ARIMA_OK) rc = xring.ensure(sts::kExpressRingBytes);
+        if (rc == ARIMA_OK) rc = xready.ensure(sts::kExpressReadyBytes);
+        return rc;
+    }
 };
 
 // One lane of the order search's concurrent fits (arima_order_search_batch*): its own stream, workspace and
@@ -79,6 +109,10 @@ struct SearchLane {
     bool sel_recorded = false;
     FitWs ws;
     DevBuf coef, ll, status, neval, ngrad, flags;
+    FitOut out() const {
+        return {coef.as<double>(), ll.as<double>(), status.as<int32_t>(), neval.as<int32_t>(), ngrad.as<int32_t>(),
+                flags.as<uint8_t>()};
+    }
     DevBuf best_aic, best_order, best_coef;    // this lane's best candidate per series (merged at the end)
     DevBuf acc;                                // kCtlWords counter sums over the lane's fits + their flops (double)
 };
@@ -86,15 +120,15 @@ struct SearchLane {
 // A device fit larger than one slice (option "fit_slice_bytes" of differenced workspace; default 0 = 60 % of the free
 // HBM over the fit contexts) runs as consecutive slices over the fit contexts: the workspaces stay bounded whatever
 // the batch (C3's 8M series on one GPU), and the slices pipeline like consecutive calls. Every slice takes the next slot of a ring with
-// its own timing events and its own pinned copy of the kernel counters, so the call's stats cover every slice. A
+// its own fit record (timing events, pinned copy of the kernel counters), so the call's stats cover every slice. A
 // slot is reused only once its previous slice's copy has landed (host check on its last event).
 constexpr int kSliceSlots = 64;
 struct SliceSlot {
-    hipEvent_t ev[5] = {};                 // start, after differencing, after init, after fit, after the counter copy
+    FitRecord rec;
     bool used = false;
-    PendingStats ps;
 };
 
+enum class StatsFrom { kNone, kContext, kSlices, kSearch };
 constexpr int kMaxSearchLanes = sts::kSearchMaxLanes;
 constexpr int kMaxD = 16;
 constexpr int kMaxPipeline = 8;
@@ -120,17 +154,19 @@ struct Inflight {                  // the device-fit calls on one context that m
 
 struct FitCtx {
     hipStream_t stream = nullptr;
-    hipEvent_t ev[kNumEvents] = {};
+    FitRecord rec;                            // of its last whole fit (a slice records into its slot instead)
     hipEvent_t ev_done = nullptr;             // end of this context's last call
     bool has_done = false;
     Inflight inflight;                        // its device-fit calls' caller buffers (fit_pipeline > 1)
     DevBuf diff;
     FitWs ws;
-    unsigned long long *ctl_host = nullptr;   // pinned
-    PendingStats pending;
-    bool fit_ctl = false;                     // ctl_host holds (or will hold, in stream order) the kernel counters
+    bool fit_ctl = false;                     // rec.ctl_host holds (or will hold, in stream order) the kernel counters
     // host path (arima_fit_batch): device copies of one chunk and pinned staging of its input and outputs
     DevBuf d_series, d_coef, d_ll, d_status, d_neval, d_ngrad, d_flags, d_uinit;
+    FitOut dev_out() const {
+        return {d_coef.as<double>(), d_ll.as<double>(), d_status.as<int32_t>(), d_neval.as<int32_t>(),
+                d_ngrad.as<int32_t>(), d_flags.as<uint8_t>()};
+    }
     void *pin = nullptr;
     size_t pin_bytes = 0;
     int64_t chunk_first = -1, chunk_n = 0;    // the chunk whose results wait in `pin`
@@ -210,11 +246,14 @@ struct arima_handle {
     SliceSlot slot[kSliceSlots];
     unsigned long long *slot_ctl = nullptr;     // pinned, kCtlWords per slot
     unsigned slot_seq = 0;                      // slots taken so far
-    unsigned slice_first = 0, slice_n = 0;      // slots of the last sliced fit call still pending (stats_ctx == -2)
+    unsigned slice_first = 0, slice_n = 0;      // slots of the last sliced fit call still pending (StatsFrom::kSlices)
     arima_fit_stats slice_acc{};                // ... and the stats of its slices whose slots were already reused
     DevBuf dev_fault;                           // sticky device record of the first fit-kernel fault (6 words)
     unsigned fit_seq = 0;          // fit calls so far (selects the context)
-    int stats_ctx = -1;            // context of the last fit (arima_get_last_stats), -1: none
+    // what arima_get_last_stats still has to complete: nothing (h->stats is final), the record of context stats_ctx,
+    // the slots of a sliced fit, or the lanes' sums of an order search
+    StatsFrom stats_from = StatsFrom::kNone;
+    int stats_ctx = 0;
     arima_fit_stats host_acc{};    // host path: counters summed over its chunks
     FitCtx fctx[kMaxPipeline];
     // device workspaces of the building blocks
@@ -301,36 +340,23 @@ __global__ void k_fault_take(unsigned long long *__restrict__ rec) {
 }
 
 // One grid point's fit into its search lane's counter sums (order-search stats, arima_get_last_stats): every kernel
-// counter word, and the fit's algorithmic flops by compute_stats' formula. cg = 0: the AR-only
-// shortcut or a uniform status (no counters; every series written). The fault words ctl[26..31] are not summed: the
-// lane keeps the first fault any of its fits recorded.
+// counter word and the fit's algorithmic flops (fit_stats.hpp search_acc_fit, which leaves the Hannan-Rissanen term
+// out for AR-only fits; a fit's own stats count it there, fit_stats).
 __global__ void k_search_acc(const unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ acc,
                              int64_t N, int n, int p, int q, int I, int cg) {
-    if (threadIdx.x != 0) return;
-    for (int i = 0; i < kCtlWords; ++i)
-        if (i < 26 || i > 31) acc[i] += ctl[i];
-    if (acc[26] == 0 && ctl[26] != 0)
-        for (int i = 26; i <= 31; ++i) acc[i] = ctl[i];
-    if (!cg) acc[32] += (unsigned long long)N;
-    const int k = I + p + q, M = p > q ? p : q, m = M + 1;
-    const double S = n - M > 0 ? n - M : 0;
-    const double ff = 2.0 * (p + q) + 4, fg = ff + 2.0 * k * q + 1 + p + q + 2.0 * k;
-    const double U = (double)(ctl[1] + ctl[18] + ctl[24] + ctl[7]), G = (double)(ctl[2] - ctl[18] + ctl[25]);
-    // the AR-only shortcut (p > 0, q == 0) runs one OLS, not the Hannan-Rissanen init
-    const bool ar_only = p > 0 && q == 0;
-    const double whr = ar_only ? 0.0
-                               : (double)N * (3.0 * (n - m > 0 ? n - m : 0) * (m + 1) * (m + 1) +
-                                              3.0 * (n - 2 * M - 1 > 0 ? n - 2 * M - 1 : 0) * k * k +
-                                              2.0 * (n - m > 0 ? n - m : 0) * m);
-    double *fl = reinterpret_cast<double *>(acc + kCtlWords);
-    *fl = *fl + U * S * ff + G * S * fg + whr;
+    if (threadIdx.x == 0) search_acc_fit(ctl, acc, N, n, p, q, I, cg);
 }
 
-// the first watchdog fault of a fit kernel (its ctl[26..31]) into the handle's sticky device record
+// the first watchdog fault of a fit kernel (its fault words) into the handle's sticky device record
 __global__ void k_fault_merge(const unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ rec) {
-    if (threadIdx.x != 0 || ctl[26] == 0) return;
-    if (atomicCAS(&rec[0], 0ull, ctl[26]) == 0ull)
-        for (int i = 1; i < 6; ++i) rec[i] = ctl[26 + i];
+    if (threadIdx.x != 0 || ctl[kCtlFault] == 0) return;
+    if (atomicCAS(&rec[0], 0ull, ctl[kCtlFault]) == 0ull)
+        for (int i = 1; i < kFaultWords; ++i) rec[i] = ctl[kCtlFault + i];
+}
+
+// what the KPSS test reports for every row of length T before it looks at one (kpsstest on no or one observation)
+int32_t kpss_shape_status(int32_t T) {
+    return T <= 0 ? ARIMA_ST_NO_DATA : (T < 2 ? ARIMA_ST_NOT_ENOUGH_DATA : ARIMA_ST_OK);
 }
 
 // p, q <= 5: the order-specialised kernels; 5 < p, q <= kGenMaxOrder (20): the runtime-order path (arima_generic.hip)
@@ -516,15 +542,15 @@ int arima_create(int device, arima_handle **out) {
     if (rc == ARIMA_OK && hipEventCreateWithFlags(&h->ev_done, hipEventDisableTiming) != hipSuccess) rc = ARIMA_E_DEVICE;
     for (auto &c : h->fctx) {
         if (rc == ARIMA_OK && hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) rc = ARIMA_E_DEVICE;
-        for (auto &e : c.ev)
-            if (rc == ARIMA_OK && hipEventCreate(&e) != hipSuccess) rc = ARIMA_E_DEVICE;
+        if (rc == ARIMA_OK) rc = c.rec.create();
         if (rc == ARIMA_OK && hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming) != hipSuccess) rc = ARIMA_E_DEVICE;
-        if (rc == ARIMA_OK && hipHostMalloc((void **)&c.ctl_host, kCtlWords * sizeof(unsigned long long), 0) != hipSuccess)
+        if (rc == ARIMA_OK && hipHostMalloc((void **)&c.rec.ctl_host, kCtlWords * sizeof(unsigned long long), 0) != hipSuccess)
             rc = ARIMA_E_OOM;
     }
     if (rc == ARIMA_OK &&
         hipHostMalloc((void **)&h->slot_ctl, (size_t)kSliceSlots * kCtlWords * sizeof(unsigned long long), 0) != hipSuccess)
         rc = ARIMA_E_OOM;
+    for (int j = 0; j < kSliceSlots && rc == ARIMA_OK; ++j) h->slot[j].rec.ctl_host = h->slot_ctl + (size_t)j * kCtlWords;
     if (rc == ARIMA_OK && hipHostMalloc((void **)&h->search_acc_host,
                                         (size_t)kMaxSearchLanes * (kCtlWords + 1) * sizeof(unsigned long long), 0) != hipSuccess)
         rc = ARIMA_E_OOM;
@@ -556,19 +582,16 @@ int arima_destroy(arima_handle *h) {
             hipStreamSynchronize(c.stream);
             hipStreamDestroy(c.stream);
         }
-        for (auto &e : c.ev)
-            if (e) hipEventDestroy(e);
+        c.rec.destroy();
         if (c.ev_done) hipEventDestroy(c.ev_done);
         for (auto &e : c.inflight.ev)
             if (e) hipEventDestroy(e);
-        if (c.ctl_host) hipHostFree(c.ctl_host);
+        if (c.rec.ctl_host) hipHostFree(c.rec.ctl_host);
         if (c.pin) hipHostFree(c.pin);
     }
     for (auto &e : h->ev_diff)
         if (e) hipEventDestroy(e);
-    for (auto &sl : h->slot)
-        for (auto &e : sl.ev)
-            if (e) hipEventDestroy(e);
+    for (auto &sl : h->slot) sl.rec.destroy();
     for (int j = 0; j < arima_handle::kStageSlots; ++j) {
         if (h->stage_ev[j]) {
             hipEventSynchronize(h->stage_ev[j]);
@@ -590,95 +613,58 @@ int arima_destroy(arima_handle *h) {
 
 const char *arima_last_error(const arima_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
-static void finish_stats(arima_handle *h, FitCtx &c);
-static arima_fit_stats compute_stats(const PendingStats &ps, const unsigned long long *cc, const hipEvent_t *ev);
-static void acc_stats(arima_fit_stats &a, const arima_fit_stats &s);
-
+// Completes h->stats from where the last call left them (StatsFrom): the sources are consumed, a second call
+// returns the same values.
 int arima_get_last_stats(const arima_handle *hc, arima_fit_stats *out) {
     if (!hc || !out) return ARIMA_E_INVALID_ARG;
     arima_handle *h = const_cast<arima_handle *>(hc);   // the lazy completion below only fills h->stats
     std::lock_guard<std::mutex> lk(h->mu);
-    if (h->stats_ctx >= 0 && h->fctx[h->stats_ctx].pending.valid) {
+    hipError_t e = hipSuccess;
+    if (h->stats_from == StatsFrom::kContext && h->fctx[h->stats_ctx].rec.ps.valid) {
         FitCtx &c = h->fctx[h->stats_ctx];
         hipSetDevice(h->device);
-        if (hipEventSynchronize(c.ev_done) != hipSuccess) return set_err(h, ARIMA_E_DEVICE, "stats: device error");
-        finish_stats(h, c);
-    } else if (h->stats_ctx == -2 && h->slice_n > 0) {   // a sliced fit: the sum over its slices
+        if ((e = hipEventSynchronize(c.ev_done)) == hipSuccess) h->stats = c.rec.stats();
+        if (e == hipSuccess) c.rec.ps.valid = false;
+    } else if (h->stats_from == StatsFrom::kSlices && h->slice_n > 0) {   // a sliced fit: the sum over its slices
         hipSetDevice(h->device);
         arima_fit_stats acc = h->slice_acc;
-        for (unsigned j = 0; j < h->slice_n; ++j) {
-            const unsigned sl = (h->slice_first + j) % kSliceSlots;
-            SliceSlot &ss = h->slot[sl];
-            if (hipEventSynchronize(ss.ev[4]) != hipSuccess) return set_err(h, ARIMA_E_DEVICE, "stats: device error");
-            acc_stats(acc, compute_stats(ss.ps, h->slot_ctl + (size_t)sl * kCtlWords, ss.ev));
+        for (unsigned j = 0; j < h->slice_n && e == hipSuccess; ++j) {
+            const FitRecord &r = h->slot[(h->slice_first + j) % kSliceSlots].rec;
+            if ((e = hipEventSynchronize(r.ev[4])) == hipSuccess) acc_stats(acc, r.stats());
         }
-        h->stats = acc;
-        h->slice_n = 0;
-        h->slice_acc = arima_fit_stats{};
-    } else if (h->stats_ctx == -3 && h->search_lanes_used > 0) {   // an order search: the sums over its fits
+        if (e == hipSuccess) {
+            h->stats = acc;
+            h->slice_n = 0;
+            h->slice_acc = arima_fit_stats{};
+        }
+    } else if (h->stats_from == StatsFrom::kSearch && h->search_lanes_used > 0) {   // the sums over a search's fits
         hipSetDevice(h->device);
-        if (hipEventSynchronize(h->ev[4]) != hipSuccess) return set_err(h, ARIMA_E_DEVICE, "stats: device error");
-        arima_fit_stats st{};
-        double flops = 0.0;
-        unsigned long long w[kCtlWords] = {};
-        for (int j = 0; j < h->search_lanes_used; ++j) {
-            const unsigned long long *a = h->search_acc_host + (size_t)j * (kCtlWords + 1);
-            for (int i = 0; i < kCtlWords; ++i)
-                if (i < 26 || i > 31) w[i] += a[i];
-            if (w[26] == 0 && a[26] != 0)                    // the first lane's recorded fault
-                for (int i = 26; i <= 31; ++i) w[i] = a[i];
-            double f;
-            memcpy(&f, a + kCtlWords, sizeof f);
-            flops += f;
+        if ((e = hipEventSynchronize(h->ev[4])) == hipSuccess) {
+            float ms = 0;
+            hipEventElapsedTime(&ms, h->ev[0], h->ev[3]);
+            h->stats = search_stats(h->search_acc_host, h->search_lanes_used, h->search_n * h->search_fits,
+                                    h->last_grid, h->last_express, ms);
+            h->search_lanes_used = 0;
         }
-        st.n_series = h->search_n * h->search_fits;          // fits (series x grid points)
-        st.f_passes = (int64_t)w[1];
-        st.g_passes = (int64_t)w[2];
-        st.wave_f_passes = (int64_t)w[3];
-        st.wave_g_passes = (int64_t)w[4];
-        st.n_eval = (int64_t)w[5];
-        st.n_grad = (int64_t)w[6];
-        st.spec_hits = (int64_t)w[7];
-        st.wave_multi_passes = (int64_t)w[8];
-        st.spec_chains = (int64_t)w[9];
-        st.ride_passes = (int64_t)w[18];
-        st.express_series = (int64_t)w[23];
-        st.express_f_passes = (int64_t)w[24];
-        st.express_g_passes = (int64_t)w[25];
-        st.series_done = (int64_t)w[32];
-        st.express_pit_passes = (int64_t)w[33];
-        st.express_pit_sweeps = (int64_t)w[34];
-        st.express_pit_g_passes = (int64_t)w[35];
-        st.wave_chains = (int64_t)w[36];
-        st.low_util_passes = (int64_t)w[37];
-        st.merge_series = (int64_t)w[41];
-        st.merge_waves = (int64_t)w[42];
-        st.fault = (int64_t)w[26];
-        for (int i = 0; i < 5; ++i) st.fault_info[i] = (int64_t)w[27 + i];
-        st.grid_blocks = h->last_grid;
-        st.express_blocks = h->last_express;
-        st.flops = flops;
-        float ms = 0;
-        hipEventElapsedTime(&ms, h->ev[0], h->ev[3]);
-        st.ms_cg_fit = ms;
-        st.ms_total = ms;
-        h->stats = st;
-        h->search_lanes_used = 0;
     }
+    if (e != hipSuccess) return set_err(h, ARIMA_E_DEVICE, "stats: device error");
     *out = h->stats;
     return ARIMA_OK;
 }
 
+// the message of a fit kernel's watchdog fault record (its six fault words)
+static int report_fault(arima_handle *h, const unsigned long long *f) {
+    char msg[160];
+    snprintf(msg, sizeof msg, "fit kernel watchdog fault %llu (info %llu %llu %llu %llu %llu)", f[0], f[1], f[2], f[3],
+             f[4], f[5]);
+    return set_err(h, ARIMA_E_DEVICE, msg);
+}
+
 // A finished fit kernel of context c recorded a watchdog fault (k_cg_fit's hand-off): its results are incomplete.
 static int check_fault(arima_handle *h, FitCtx &c) {
-    if (c.fit_ctl && c.ctl_host[26] != 0) {
-        c.fit_ctl = false;                      // reported once
-        char msg[160];
-        snprintf(msg, sizeof msg, "fit kernel watchdog fault %llu (info %llu %llu %llu %llu %llu)", c.ctl_host[26],
-                 c.ctl_host[27], c.ctl_host[28], c.ctl_host[29], c.ctl_host[30], c.ctl_host[31]);
-        return set_err(h, ARIMA_E_DEVICE, msg);
-    }
-    return ARIMA_OK;
+    if (!c.fit_ctl || c.rec.ctl_host[kCtlFault] == 0) return ARIMA_OK;
+    c.fit_ctl = false;                      // reported once
+    return report_fault(h, c.rec.ctl_host + kCtlFault);
 }
 
 static int take_fault(arima_handle *h);
@@ -829,18 +815,17 @@ static hipEvent_t order_after_overlapping_fits(arima_handle *h, int ci, const Ca
 }
 
 static CallSpans call_spans(const double *series, int64_t N, int32_t T, int64_t ld, int k, const double *uinit,
-                            const double *coef, const double *ll, const int32_t *st, const int32_t *ne,
-                            const int32_t *ng, const uint8_t *fl) {
+                            const FitOut &o) {
     CallSpans cs;
     if (N <= 0) return cs;
     cs.in[0] = ByteSpan(series, ((N - 1) * ld + std::max<int64_t>(T, 0)) * (int64_t)sizeof(double));
     cs.in[1] = ByteSpan(uinit, N * k * (int64_t)sizeof(double));
-    cs.out[0] = ByteSpan(coef, N * k * (int64_t)sizeof(double));
-    cs.out[1] = ByteSpan(ll, N * (int64_t)sizeof(double));
-    cs.out[2] = ByteSpan(st, N * (int64_t)sizeof(int32_t));
-    cs.out[3] = ByteSpan(ne, N * (int64_t)sizeof(int32_t));
-    cs.out[4] = ByteSpan(ng, N * (int64_t)sizeof(int32_t));
-    cs.out[5] = ByteSpan(fl, N);
+    cs.out[0] = ByteSpan(o.coef, N * k * (int64_t)sizeof(double));
+    cs.out[1] = ByteSpan(o.ll, N * (int64_t)sizeof(double));
+    cs.out[2] = ByteSpan(o.status, N * (int64_t)sizeof(int32_t));
+    cs.out[3] = ByteSpan(o.n_eval, N * (int64_t)sizeof(int32_t));
+    cs.out[4] = ByteSpan(o.n_grad, N * (int64_t)sizeof(int32_t));
+    cs.out[5] = ByteSpan(o.flags, N);
     return cs;
 }
 
@@ -850,24 +835,28 @@ static hipError_t end_fit(FitCtx &c, hipStream_t s) {
     return e;
 }
 
+struct FitOpts {                   // how fit_kernels runs its fit
+    // other fits run concurrently (the order search's lanes, pipelined calls), so the fit kernel's drained workgroups
+    // exit instead of joining its express pool
+    bool shared_gpu = false;
+    int express_cus = -2;          // the fit kernel's express CUs; -2 = the "express_blocks" option (the search passes its own)
+    bool search = false;           // a lane of the order search: k_hr_init keeps a lane per series
+    // 1: y holds the caller's RAW rows (leading dimension ldn) of a d = 1 fit, differenced inside every pass (fused
+    // differencing, arima_device.hpp stream_row); 0: y holds differenced rows
+    int dd = 0;
+    hipEvent_t ev_mid = nullptr;   // recorded between the init and the fit kernel
+};
+
 // Hannan-Rissanen init (unless user init) and the fit kernel -- or the AR-only shortcut, or a uniform per-series
 // status -- over already-differenced rows y (N x n, leading dimension ldn), on stream s with workspace ws.
-// ev_mid (optional) is recorded between the init and the fit kernel. shared_gpu: other fits run concurrently (the
-// order search's lanes), so the fit kernel's drained workgroups exit instead of joining its express pool.
-// dd = 1: y holds the caller's RAW rows (leading dimension ldn) of a d = 1 fit, differenced inside every pass (fused
-// differencing, arima_device.hpp stream_row); dd = 0: y holds differenced rows.
 static int fit_kernels(arima_handle *h, FitWs &ws, const double *y, int64_t ldn, int n, int64_t N, int32_t p,
-                       int32_t q, int32_t I, int32_t method, const double *d_user_init, double *d_coef, double *d_ll,
-                       int32_t *d_status, int32_t *d_neval, int32_t *d_ngrad, uint8_t *d_flags, hipStream_t s,
-                       hipEvent_t ev_mid, int64_t *grid_out, int64_t *express_out, bool shared_gpu = false,
-                       int express_cus = -2, bool search = false, int dd = 0) {
+                       int32_t q, int32_t I, int32_t method, const double *d_user_init, const FitOut &o, hipStream_t s,
+                       int64_t *grid_out, int64_t *express_out, const FitOpts &opt = FitOpts{}) {
     const int k = I + p + q;
+    const int dd = opt.dd;
     *grid_out = 0;
     *express_out = 0;
-    // every workspace before the first launch (a growing DevBuf frees, and hipFree synchronises the device)
-    RCCHK(h, ws.ctl.ensure(kCtlWords * sizeof(unsigned long long)), "workspace");
-    RCCHK(h, ws.xring.ensure(sts::kExpressRingBytes), "workspace");
-    RCCHK(h, ws.xready.ensure(sts::kExpressReadyBytes), "workspace");
+    RCCHK(h, ws.reserve(N, k), "workspace");
     // the fit kernel's counters and express-ring ready words, initialised by the kernel that runs before it
     // (k_hr_init, or one k_fit_prep dispatch) instead of up to six fill dispatches (round 6)
     sts::FitPrep prep;
@@ -884,36 +873,29 @@ static int fit_kernels(arima_handle *h, FitWs &ws, const double *y, int64_t ldn,
     if (!cg || gen) prep.xready_words = 0;                     // no express ring: only the counters are read
     if (p > 0 && q == 0) {                                     // AR-only shortcut, method never checked
         RCCHK(h, sts::launch_fit_prep(prep, s), "fit_prep");
-        if (ev_mid) HIPCHK(h, hipEventRecord(ev_mid, s));
-        if (gen)
-            RCCHK(h, sts::launch_gen_ar_fit(y, ldn, n, N, p, I, d_coef, d_ll, d_status, d_neval, d_ngrad, d_flags, dd,
-                                            s), "ar_fit");
-        else
-            RCCHK(h, sts::launch_ar_fit(y, ldn, n, N, p, I, d_coef, d_ll, d_status, d_neval, d_ngrad, d_flags, s, dd),
-                  "ar_fit");
+        if (opt.ev_mid) HIPCHK(h, hipEventRecord(opt.ev_mid, s));
+        if (gen) RCCHK(h, sts::launch_gen_ar_fit(y, ldn, n, N, p, I, o, dd, s), "ar_fit");
+        else RCCHK(h, sts::launch_ar_fit(y, ldn, n, N, p, I, o, s, dd), "ar_fit");
         return ARIMA_OK;
     }
     const double *init = d_user_init;
     const int32_t *init_status = nullptr;
     if (!d_user_init) {
-        RCCHK(h, ws.init.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "workspace");
-        RCCHK(h, ws.hr_status.ensure((size_t)N * sizeof(int32_t)), "workspace");
         if (gen)
             RCCHK(h, sts::launch_gen_hr_init(y, ldn, n, N, p, q, I, ws.init.as<double>(), ws.hr_status.as<int32_t>(),
                                              dd, prep, s), "hr_init");
         else
             RCCHK(h, sts::launch_hr_init(y, ldn, n, N, p, q, I, ws.init.as<double>(), ws.hr_status.as<int32_t>(), s,
-                                         h->hr_grid >= 0 ? h->hr_grid : (shared_gpu && !search ? 1024 : 0), dd, prep),
-                  "hr_init");
+                                         h->hr_grid >= 0 ? h->hr_grid : (opt.shared_gpu && !opt.search ? 1024 : 0), dd,
+                                         prep), "hr_init");
         init = ws.init.as<double>();
         init_status = ws.hr_status.as<int32_t>();
     } else {
         RCCHK(h, sts::launch_fit_prep(prep, s), "fit_prep");
     }
-    if (ev_mid) HIPCHK(h, hipEventRecord(ev_mid, s));
+    if (opt.ev_mid) HIPCHK(h, hipEventRecord(opt.ev_mid, s));
     if (method == ARIMA_METHOD_CSS_BOBYQA && k > 0) {           // fitWithCSSBOBYQA, ARIMA.scala:106, :130-160
-        RCCHK(h, sts::launch_bobyqa_fit(y, ldn, n, N, p, q, I, init, init_status, nullptr, d_coef, d_ll, d_status,
-                                        d_neval, d_ngrad, d_flags,
+        RCCHK(h, sts::launch_bobyqa_fit(y, ldn, n, N, p, q, I, init, init_status, nullptr, o,
                                         h->bobyqa_wave < 0 ? N <= kBobyqaWaveMaxN : h->bobyqa_wave != 0, s),
               "bobyqa_fit");
         return ARIMA_OK;
@@ -921,22 +903,21 @@ static int fit_kernels(arima_handle *h, FitWs &ws, const double *y, int64_t ldn,
     if (method != ARIMA_METHOD_CSS_CGD || k == 0) {
         const unsigned grid = (unsigned)((N + 255) / 256);
         const int32_t code = (method != ARIMA_METHOD_CSS_CGD) ? ARIMA_ST_UNSUPPORTED_METHOD : ARIMA_ST_ZERO_PARAMS;
-        hipLaunchKernelGGL(k_fill_status, dim3(grid), dim3(256), 0, s, N, k, init_status, code, d_coef, d_ll,
-                           d_status, d_neval, d_ngrad, d_flags);
+        hipLaunchKernelGGL(k_fill_status, dim3(grid), dim3(256), 0, s, N, k, init_status, code, o.coef, o.ll, o.status,
+                           o.n_eval, o.n_grad, o.flags);
         HIPCHK(h, hipGetLastError());
         return ARIMA_OK;
     }
     if (gen) {                                                  // fitWithCSSCGD at runtime orders, a lane per series
-        RCCHK(h, sts::launch_gen_fit(y, ldn, n, N, p, q, I, h->smear, init, init_status, d_coef, d_ll, d_status,
-                                     d_neval, d_ngrad, d_flags, ws.ctl.as<unsigned long long>(), dd, s), "gen_fit");
+        RCCHK(h, sts::launch_gen_fit(y, ldn, n, N, p, q, I, h->smear, init, init_status, o,
+                                     ws.ctl.as<unsigned long long>(), dd, s), "gen_fit");
         return ARIMA_OK;
     }
     // one persistent workgroup per CU (4 waves x the kernel's optimizer slots), the last num_cus/16 of them express
     // workgroups (k_cg_fit's long-series path); fewer bulk blocks when the batch cannot fill them
     // (express_blocks and grid_blocks count CUs' worth of workgroups: x kFitBlocksPerCU single-wave workgroups)
     const int cus = std::max(1, h->num_cus);
-    // (express_cus: the caller's count, -2 = the "express_blocks" option; the order search passes its own)
-    const int xopt = express_cus >= -1 ? express_cus : h->express_blocks;
+    const int xopt = opt.express_cus >= -1 ? opt.express_cus : h->express_blocks;
     int xcus = xopt >= 0 ? xopt : std::max(1, cus / 16);
     if (xcus >= cus) xcus = cus - 1;
     int bcus = h->grid_blocks_override;
@@ -949,10 +930,9 @@ static int fit_kernels(arima_handle *h, FitWs &ws, const double *y, int64_t ldn,
     if (blocks > need) blocks = (int)need;
     *grid_out = blocks;
     *express_out = xcus;                    // in CUs, the unit of the "express_blocks" option
-    RCCHK(h, sts::launch_cg_fit(y, ldn, n, N, p, q, I, h->smear, init, init_status, d_coef, d_ll, d_status, d_neval,
-                                d_ngrad, d_flags, ws.ctl.as<unsigned long long>(), blocks, xblocks,
-                                ws.xring.as<unsigned char>(), ws.xready.as<unsigned>(), shared_gpu ? 0 : 1, s, dd),
-          "cg_fit");
+    RCCHK(h, sts::launch_cg_fit(y, ldn, n, N, p, q, I, h->smear, init, init_status, o, ws.ctl.as<unsigned long long>(),
+                                blocks, xblocks, ws.xring.as<unsigned char>(), ws.xready.as<unsigned>(),
+                                opt.shared_gpu ? 0 : 1, s, dd), "cg_fit");
     hipLaunchKernelGGL(k_fault_merge, dim3(1), dim3(64), 0, s, ws.ctl.as<unsigned long long>(),
                        h->dev_fault.as<unsigned long long>());
     HIPCHK(h, hipGetLastError());
@@ -965,36 +945,22 @@ static int reserve_fit_ws(arima_handle *h, int count, int64_t N, int64_t ldn, in
     for (int j = 0; j < count; ++j) {
         FitCtx &c = h->fctx[j];
         if (diff_ws) RCCHK(h, c.diff.ensure((size_t)N * ldn * sizeof(double)), "workspace");
-        RCCHK(h, c.ws.init.ensure((size_t)N * std::max(k, 1) * sizeof(double)), "workspace");
-        RCCHK(h, c.ws.hr_status.ensure((size_t)N * sizeof(int32_t)), "workspace");
-        RCCHK(h, c.ws.ctl.ensure(kCtlWords * sizeof(unsigned long long)), "workspace");
-        RCCHK(h, c.ws.xring.ensure(sts::kExpressRingBytes), "workspace");
-        RCCHK(h, c.ws.xready.ensure(sts::kExpressReadyBytes), "workspace");
+        RCCHK(h, c.ws.reserve(N, k), "workspace");
     }
     return ARIMA_OK;
 }
 
-// One fit on context c, enqueued on stream s (the caller has ordered s after what the fit depends on).
+// One fit on context c, enqueued on stream s: the caller has checked the arguments, selected the device and ordered s
+// after what the fit depends on. Its timing events and counter copy go to rec: the context's own record, or the slot
+// record of one slice of a sliced call (the context then keeps no pending stats of its own).
 // shared_gpu: fits of other contexts may run concurrently, so the fit kernel's drained workgroups exit (making room
 // for the next fit) instead of joining its express pool.
-// slot >= 0: one slice of a sliced call -- timing events and the counter copy go to that slice slot, and the
-// context keeps no pending stats of its own.
-static int fit_device_locked(arima_handle *h, FitCtx &c, int ci, int reserve, const double *d_series, int64_t N,
+static int fit_device_locked(arima_handle *h, FitCtx &c, FitRecord &rec, int reserve, const double *d_series, int64_t N,
                              int32_t T, int64_t ld, int32_t p, int32_t d, int32_t q, int32_t I, int32_t method,
-                             const double *d_user_init, double *d_coef, double *d_ll, int32_t *d_status,
-                             int32_t *d_neval, int32_t *d_ngrad, uint8_t *d_flags, hipStream_t s, bool shared_gpu,
-                             int slot = -1) {
-    RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    if (N < 0 || T < 0 || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    if (!d_coef || !d_ll || !d_status) return set_err(h, ARIMA_E_INVALID_ARG, "null output");
-    HIPCHK(h, hipSetDevice(h->device));
+                             const double *d_user_init, const FitOut &o, hipStream_t s, bool shared_gpu) {
     const int k = I + p + q;
     const int n = std::max(T - d, 0);
-    c.pending = PendingStats{};
-    if (slot < 0) {
-        h->stats = arima_fit_stats{};
-        h->stats_ctx = ci;
-    }
+    c.rec.ps = rec.ps = FitShape{};
     if (N == 0) return ARIMA_OK;
     // Fused differencing (round 6): css-cgd fits (and the AR-only shortcut) of d <= 1 read the caller's rows directly
     // -- d = 0 as they are, d = 1 differenced inside every pass (arima_device.hpp stream_row) -- instead of a
@@ -1004,28 +970,25 @@ static int fit_device_locked(arima_handle *h, FitCtx &c, int ci, int reserve, co
                        (h->fuse_mode == 2 || (h->fuse_mode == 1 && sts::fuse_pays(p, q)));
     const int64_t ldn = fused ? ld : row_stride(h, n);
     const double *rows = fused ? d_series : nullptr;
-
-    SliceSlot *ss = slot >= 0 ? &h->slot[slot] : nullptr;
-    hipEvent_t *ev = ss ? ss->ev : c.ev;
-    unsigned long long *ctl_dst = ss ? h->slot_ctl + (size_t)slot * kCtlWords : c.ctl_host;
     RCCHK(h, reserve_fit_ws(h, reserve, N, ldn, k, !fused), "workspace");
-    HIPCHK(h, hipEventRecord(ev[0], s));
+    HIPCHK(h, hipEventRecord(rec.ev[0], s));
     if (!fused) {
         RCCHK(h, sts::launch_difference(d_series, ld, c.diff.as<double>(), ldn, N, T, d, 1, s), "difference");
         rows = c.diff.as<double>();
     }
-    HIPCHK(h, hipEventRecord(ev[1], s));
-    int64_t grid = 0, xblocks = 0;
-    RCCHK(h, fit_kernels(h, c.ws, rows, ldn, n, N, p, q, I, method, d_user_init, d_coef, d_ll,
-                         d_status, d_neval, d_ngrad, d_flags, s, ev[2], &grid, &xblocks, shared_gpu, -2, false,
-                         fused ? d : 0), "fit");
-    HIPCHK(h, hipEventRecord(ev[3], s));
-    h->last_grid = grid;
-    h->last_express = xblocks;
-    HIPCHK(h, hipMemcpyAsync(ctl_dst, c.ws.ctl.ptr, kCtlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    if (ss) HIPCHK(h, hipEventRecord(ss->ev[4], s));
-    c.fit_ctl = !ss;
-    PendingStats &ps = ss ? ss->ps : c.pending;
+    HIPCHK(h, hipEventRecord(rec.ev[1], s));
+    FitShape &ps = rec.ps;
+    FitOpts opt;
+    opt.shared_gpu = shared_gpu;
+    opt.dd = fused ? d : 0;
+    opt.ev_mid = rec.ev[2];
+    RCCHK(h, fit_kernels(h, c.ws, rows, ldn, n, N, p, q, I, method, d_user_init, o, s, &ps.grid, &ps.express, opt),
+          "fit");
+    HIPCHK(h, hipEventRecord(rec.ev[3], s));
+    h->last_grid = ps.grid;
+    h->last_express = ps.express;
+    HIPCHK(h, hipMemcpyAsync(rec.ctl_host, c.ws.ctl.ptr, kCtlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    c.fit_ctl = &rec == &c.rec;             // check_fault reads the context's own copy only
     ps.N = N;
     ps.n = n;
     ps.p = p;
@@ -1034,86 +997,27 @@ static int fit_device_locked(arima_handle *h, FitCtx &c, int ci, int reserve, co
     ps.ar_only = p > 0 && q == 0;
     ps.user_init = d_user_init != nullptr;
     ps.cg = !ps.ar_only && method == ARIMA_METHOD_CSS_CGD && k > 0;
-    ps.grid = grid;
-    ps.express = xblocks;
     ps.valid = true;
     return ARIMA_OK;
 }
 
-// The stats of one finished fit (or slice) from its pending shape, its counter copy and its timing events.
-static arima_fit_stats compute_stats(const PendingStats &ps, const unsigned long long *cc, const hipEvent_t *ev) {
-    arima_fit_stats st{};
-    if (!ps.valid) return st;
-    const int64_t N = ps.N;
-    const int n = ps.n, p = ps.p, q = ps.q, I = ps.I, k = I + p + q;
-    float ms = 0;
-    hipEventElapsedTime(&ms, ev[0], ev[1]);
-    st.ms_difference = ms;
-    hipEventElapsedTime(&ms, ev[1], ev[2]);
-    st.ms_hr_init = ms;
-    hipEventElapsedTime(&ms, ev[2], ev[3]);
-    st.ms_cg_fit = ms;
-    hipEventElapsedTime(&ms, ev[0], ev[3]);
-    st.ms_total = ms;
-    st.f_passes = (int64_t)cc[1];
-    st.g_passes = (int64_t)cc[2];
-    st.n_eval = (int64_t)cc[5];
-    st.n_grad = (int64_t)cc[6];
-    st.wave_f_passes = (int64_t)cc[3];
-    st.wave_g_passes = (int64_t)cc[4];
-    st.spec_hits = (int64_t)cc[7];
-    st.wave_multi_passes = (int64_t)cc[8];
-    st.spec_chains = (int64_t)cc[9];
-    st.ride_passes = (int64_t)cc[18];
-    // series the kernels wrote; the AR-only shortcut, user-uniform statuses and an empty fit write every series
-    st.series_done = ps.cg ? (int64_t)cc[32] : N;
-    st.express_series = (int64_t)cc[23];
-    st.express_f_passes = (int64_t)cc[24];
-    st.express_g_passes = (int64_t)cc[25];
-    st.express_pit_passes = (int64_t)cc[33];
-    st.express_pit_sweeps = (int64_t)cc[34];
-    st.express_pit_g_passes = (int64_t)cc[35];
-    st.wave_chains = (int64_t)cc[36];
-    st.low_util_passes = (int64_t)cc[37];
-    st.diag_step_cycles = (int64_t)cc[38];
-    st.diag_refill_cycles = (int64_t)cc[39];
-    st.merge_series = (int64_t)cc[41];
-    st.merge_waves = (int64_t)cc[42];
-    st.express_blocks = ps.express;
-    st.fault = (int64_t)cc[26];
-    for (int i = 0; i < 5; ++i) st.fault_info[i] = (int64_t)cc[27 + i];
-    // STS_TIMING builds: F-pass, G-pass, advance, select cycles (summed over waves), kernel span, drained time
-    st.diag[0] = (int64_t)cc[10];
-    st.diag[1] = (int64_t)cc[11];
-    st.diag[2] = (int64_t)cc[12];
-    st.diag[3] = (int64_t)cc[13];
-    st.diag[4] = cc[14] ? (int64_t)(cc[14] - cc[15]) : 0;
-    st.diag[5] = (int64_t)cc[16];
-    st.grid_blocks = ps.grid;
-    // HR passes: 2 per column of each of the two least squares, minus the norm pass of an intercept column (the
-    // sum of ones needs no stream; arima_device.hpp ols_stage)
-    const int M = std::max(p, q), m = M + 1;
-    if (ps.ar_only) st.hr_passes = N * (int64_t)(2 * (I + p) - I);
-    else if (!ps.user_init) st.hr_passes = N * (int64_t)(2 * (1 + m) - 1 + 2 * k - I);
-    // algorithmic flops: U*S*(2(p+q)+4) + G*S*(2(p+q)+4 + 2kq + 1+p+q + 2k) + W_HR, with
-    // U = distinct objective points evaluated by a pass (bulk objective passes, objective requests served by
-    // gradient passes, express objective passes, and the speculative points the optimizer then used) and
-    // G = gradient evaluations that ran a pass (bulk gradient passes without the objective riders, express ones)
-    const double S = std::max(n - M, 0);
-    const double ff = 2.0 * (p + q) + 4, fg = ff + 2.0 * k * q + 1 + p + q + 2.0 * k;
-    const double whr = (double)N * (3.0 * std::max(n - m, 0) * (m + 1) * (m + 1) +
-                                    3.0 * std::max(n - 2 * M - 1, 0) * k * k + 2.0 * std::max(n - m, 0) * m);
-    const double U = (double)(st.f_passes + st.ride_passes + st.express_f_passes + st.spec_hits);
-    const double G = (double)(st.g_passes - st.ride_passes + st.express_g_passes);
-    st.flops = U * S * ff + G * S * fg + (ps.user_init ? 0.0 : whr);
-    st.n_series = N;
-    return st;
-}
-
-// Completes the stats of context c's last fit once its device work has finished.
-static void finish_stats(arima_handle *h, FitCtx &c) {
-    h->stats = compute_stats(c.pending, c.ctl_host, c.ev);
-    c.pending.valid = false;
+// The record of the call's next slice: the next slot of the ring, free to overwrite. More slices than slots: the slot's
+// pending slice is the oldest of THIS call, and its stats are folded into the call's running total first.
+static int take_slice_slot(arima_handle *h, FitRecord **rec) {
+    SliceSlot &ss = h->slot[h->slot_seq++ % kSliceSlots];
+    if (!ss.used) {
+        RCCHK(h, ss.rec.create(), "slice events");
+        ss.used = true;
+    } else if (hipEventQuery(ss.rec.ev[4]) != hipSuccess) {
+        HIPCHK(h, hipEventSynchronize(ss.rec.ev[4]));       // its previous slice's counter copy must have landed
+    }
+    if (h->slice_n == (unsigned)kSliceSlots) {
+        acc_stats(h->slice_acc, ss.rec.stats());
+        h->slice_first = (h->slice_first + 1) % kSliceSlots;
+        h->slice_n--;
+    }
+    *rec = &ss.rec;
+    return ARIMA_OK;
 }
 
 int arima_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
@@ -1123,12 +1027,16 @@ int arima_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_se
                            uint8_t *d_flags_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
-    const int P = h->pipeline;
+    // (1) the argument checks: a refused call touches no device
+    const FitOut out{d_coef_out, d_css_ll_out, d_status_out, d_n_eval_out, d_n_grad_out, d_flags_out};
+    RCCHK(h, check_orders(h, p, d, q, include_intercept), "orders");
+    if (n_series < 0 || T < 0 || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (!out.coef || !out.ll || !out.status) return set_err(h, ARIMA_E_INVALID_ARG, "null output");
+    const int P = h->pipeline, k = include_intercept + p + q;
     HIPCHK(h, hipSetDevice(h->device));
-    const int64_t ldn = row_stride(h, T - d);
-    // Slice size: option fit_slice_bytes, or (0, the default) as large as the free HBM allows for P contexts. Every
-    // slice ends with its own slowest series (the launch's critical path), so fewer, larger slices are faster (C4 at
-    // 1M x 4096 in 262k-series slices: 2.9 s per fit alone, one slice: 1.2 s).
+    // (2) the slice size: option fit_slice_bytes, or (0, the default) as large as the free HBM allows for P contexts.
+    // Every slice ends with its own slowest series (the launch's critical path), so fewer, larger slices are faster
+    // (C4 at 1M x 4096 in 262k-series slices: 2.9 s per fit alone, one slice: 1.2 s).
     int64_t slice_bytes = h->fit_slice_bytes;
     if (slice_bytes <= 0) {
         size_t free_b = 0, total_b = 0;
@@ -1137,70 +1045,43 @@ int arima_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_se
         for (int j = 0; j < P; ++j) held += h->fctx[j].diff.bytes;
         slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + held) / 10 * 6 / (size_t)std::max(P, 1)));
     }
-    int64_t slice = sts::plan::fit_slice_rows(slice_bytes, ldn);
-    if (n_series <= slice || T < 0 || ld < T || n_series < 0) {
+    const int64_t slice = sts::plan::fit_slice_rows(slice_bytes, row_stride(h, T - d));
+    // (3) the slices, each on the next fit context in the rotation (its own rows of the outputs), exactly as
+    // consecutive calls. A call of one slice records into its context; a sliced one into the slots of the ring.
+    const int64_t nslices = std::max<int64_t>(1, (n_series + slice - 1) / slice);
+    const bool sliced = nslices > 1;
+    h->stats = arima_fit_stats{};
+    h->stats_from = sliced ? StatsFrom::kSlices : StatsFrom::kContext;
+    if (sliced) {
+        h->slice_first = h->slot_seq % kSliceSlots;
+        h->slice_n = 0;
+        h->slice_acc = arima_fit_stats{};
+    }
+    for (int64_t j = 0; j < nslices; ++j) {
+        FitRecord *rec = nullptr;
+        if (sliced) PASSCHK(take_slice_slot(h, &rec));
         const int ci = (int)(h->fit_seq++ % (unsigned)P);
         FitCtx &c = h->fctx[ci];
+        if (!sliced) {
+            rec = &c.rec;
+            h->stats_ctx = ci;
+        }
+        const int64_t f = j * slice, ns = std::min(slice, n_series - f);
+        const double *rows = d_series + f * ld, *uinit = d_user_init ? d_user_init + f * k : nullptr;
+        const FitOut o = out.at(f, k);
         hipStream_t s = stream ? (hipStream_t)stream : c.stream;
         begin_fit(h, c, s);
         // hazards against in-flight fits of every context, whatever P is now: fits issued under a larger
         // fit_pipeline may still run on other contexts
-        hipEvent_t ev_call = order_after_overlapping_fits(h, ci, call_spans(d_series, n_series, T, ld,
-                                                                     include_intercept + p + q, d_user_init,
-                                                                     d_coef_out, d_css_ll_out, d_status_out,
-                                                                     d_n_eval_out, d_n_grad_out, d_flags_out), s);
-        const int rc = fit_device_locked(h, c, ci, P, d_series, n_series, T, ld, p, d, q, include_intercept, method,
-                                         d_user_init, d_coef_out, d_css_ll_out, d_status_out, d_n_eval_out,
-                                         d_n_grad_out, d_flags_out, s, P > 1);
+        hipEvent_t ev_call = order_after_overlapping_fits(h, ci, call_spans(rows, ns, T, ld, k, uinit, o), s);
+        int rc = fit_device_locked(h, c, *rec, P, rows, ns, T, ld, p, d, q, include_intercept, method, uinit, o, s,
+                                   P > 1);
+        // a slot's copy has landed once this event has passed (a context's record is waited for through ev_done)
+        if (sliced && rc == ARIMA_OK && hipEventRecord(rec->ev[4], s) != hipSuccess)
+            rc = set_err(h, ARIMA_E_DEVICE, "slice event");
         HIPCHK(h, end_fit(c, s));
         if (ev_call) HIPCHK(h, hipEventRecord(ev_call, s));
-        return rc;
-    }
-    // sliced: slice j of the batch runs on the next fit context (its own outputs' rows), exactly as consecutive calls
-    RCCHK(h, check_orders(h, p, d, q, include_intercept), "orders");
-    if (!d_coef_out || !d_css_ll_out || !d_status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null output");
-    const int k = include_intercept + p + q;
-    const int64_t nslices = (n_series + slice - 1) / slice;
-    h->stats = arima_fit_stats{};
-    h->stats_ctx = -2;
-    h->slice_first = h->slot_seq % kSliceSlots;
-    h->slice_n = 0;
-    h->slice_acc = arima_fit_stats{};
-    for (int64_t j = 0; j < nslices; ++j) {
-        const int sl = (int)(h->slot_seq++ % kSliceSlots);
-        SliceSlot &ss = h->slot[sl];
-        if (!ss.used) {
-            for (auto &e : ss.ev) HIPCHK(h, hipEventCreate(&e));
-            ss.used = true;
-        } else if (hipEventQuery(ss.ev[4]) != hipSuccess) {
-            HIPCHK(h, hipEventSynchronize(ss.ev[4]));       // its previous slice's counter copy must have landed
-        }
-        if (h->slice_n == (unsigned)kSliceSlots) {
-            // more slices than slots: the oldest pending slice of THIS call is the one in slot sl; fold its stats
-            // into the call's running total before the slot is overwritten
-            acc_stats(h->slice_acc, compute_stats(ss.ps, h->slot_ctl + (size_t)sl * kCtlWords, ss.ev));
-            h->slice_first = (h->slice_first + 1) % kSliceSlots;
-            h->slice_n--;
-        }
-        ss.ps = PendingStats{};
-        const int64_t f = j * slice, ns = std::min(slice, n_series - f);
-        const int ci = (int)(h->fit_seq++ % (unsigned)P);             // the next context in the rotation
-        FitCtx &c = h->fctx[ci];
-        hipStream_t s = stream ? (hipStream_t)stream : c.stream;
-        begin_fit(h, c, s);
-        hipEvent_t ev_call = order_after_overlapping_fits(
-                h, ci, call_spans(d_series + f * ld, ns, T, ld, k, d_user_init ? d_user_init + f * k : nullptr,
-                                  d_coef_out + f * k, d_css_ll_out + f, d_status_out + f,
-                                  d_n_eval_out ? d_n_eval_out + f : nullptr, d_n_grad_out ? d_n_grad_out + f : nullptr,
-                                  d_flags_out ? d_flags_out + f : nullptr), s);
-        const int rc = fit_device_locked(
-            h, c, ci, P, d_series + f * ld, ns, T, ld, p, d, q, include_intercept, method,
-            d_user_init ? d_user_init + f * k : nullptr, d_coef_out + f * k, d_css_ll_out + f, d_status_out + f,
-            d_n_eval_out ? d_n_eval_out + f : nullptr, d_n_grad_out ? d_n_grad_out + f : nullptr,
-            d_flags_out ? d_flags_out + f : nullptr, s, P > 1, sl);
-        HIPCHK(h, end_fit(c, s));
-        if (ev_call) HIPCHK(h, hipEventRecord(ev_call, s));
-        h->slice_n++;
+        if (sliced) h->slice_n++;
         if (rc != ARIMA_OK) return rc;
     }
     return ARIMA_OK;
@@ -1213,52 +1094,7 @@ int arima_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_se
 // the tail of one chunk's fit kernel overlaps the next chunk's work. Results come back through pinned staging and
 // are copied to the caller's arrays when the context is reused (or at the end).
 // ---------------------------------------------------------------------------------------------------------
-namespace {
-struct HostOut {
-    double *coef, *ll;
-    int32_t *status, *n_eval, *n_grad;
-    uint8_t *flags;
-};
-
 using sts::plan::pin_layout;   // one chunk's results in pinned staging (host_plan.hpp)
-}  // namespace
-
-static void acc_stats(arima_fit_stats &a, const arima_fit_stats &s) {
-    a.ms_difference += s.ms_difference;
-    a.ms_hr_init += s.ms_hr_init;
-    a.ms_cg_fit += s.ms_cg_fit;
-    a.ms_total += s.ms_total;
-    a.f_passes += s.f_passes;
-    a.g_passes += s.g_passes;
-    a.hr_passes += s.hr_passes;
-    a.n_eval += s.n_eval;
-    a.n_grad += s.n_grad;
-    a.flops += s.flops;
-    a.n_series += s.n_series;
-    a.wave_f_passes += s.wave_f_passes;
-    a.wave_g_passes += s.wave_g_passes;
-    a.wave_multi_passes += s.wave_multi_passes;
-    a.spec_hits += s.spec_hits;
-    a.spec_chains += s.spec_chains;
-    a.ride_passes += s.ride_passes;
-    a.series_done += s.series_done;
-    a.express_series += s.express_series;
-    a.express_f_passes += s.express_f_passes;
-    a.express_g_passes += s.express_g_passes;
-    a.express_pit_passes += s.express_pit_passes;
-    a.express_pit_sweeps += s.express_pit_sweeps;
-    a.express_pit_g_passes += s.express_pit_g_passes;
-    a.wave_chains += s.wave_chains;
-    a.low_util_passes += s.low_util_passes;
-    a.merge_series += s.merge_series;
-    a.merge_waves += s.merge_waves;
-    a.grid_blocks = s.grid_blocks;
-    a.express_blocks = s.express_blocks;
-    if (!a.fault && s.fault) {
-        a.fault = s.fault;
-        for (int i = 0; i < 5; ++i) a.fault_info[i] = s.fault_info[i];
-    }
-}
 
 // Host rows -> device on stream s through the handle's ring of pinned blocks: block i is filled by the copy threads
 // while block i-1's DMA runs; a block is refilled only after its previous DMA has finished (its event). The caller's
@@ -1289,15 +1125,15 @@ static int upload_staged(arima_handle *h, void *dst, const void *src, size_t byt
 }
 
 // Wait for context c's chunk, copy its results to the caller's arrays and add its counters to h->host_acc.
-static int drain_chunk(arima_handle *h, FitCtx &c, int k, const HostOut &o) {
+static int drain_chunk(arima_handle *h, FitCtx &c, int k, const FitOut &o) {
     if (c.chunk_n <= 0) return ARIMA_OK;
     HIPCHK(h, hipEventSynchronize(c.ev_done));
     const int64_t f = c.chunk_first, n = c.chunk_n;
     c.chunk_n = 0;
     // this chunk's own stats (zeros if its fit left none), never whatever h->stats holds from another chunk
-    const bool kernel_counters = c.pending.valid && c.pending.cg;
-    arima_fit_stats st = compute_stats(c.pending, c.ctl_host, c.ev);
-    c.pending.valid = false;
+    const bool kernel_counters = c.rec.ps.valid && c.rec.ps.cg;
+    arima_fit_stats st = c.rec.stats();
+    c.rec.ps.valid = false;
     size_t off[6];
     pin_layout(n, k, off);
     const char *b = static_cast<const char *>(c.pin);
@@ -1333,7 +1169,7 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
     if (N < 0 || T < 0 || (N > 0 && (!series || !coef_out || !css_ll_out || !status_out)))
         return set_err(h, ARIMA_E_INVALID_ARG, "bad arguments");
     h->stats = arima_fit_stats{};
-    h->stats_ctx = -1;
+    h->stats_from = StatsFrom::kNone;
     if (N == 0) return ARIMA_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const int k = I + p + q;
@@ -1346,7 +1182,7 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
     const int64_t chunk = sts::plan::max_chunk(starts);
     const int64_t nchunks = (int64_t)starts.size() - 1;
     const int used = (int)std::min<int64_t>(P, nchunks);
-    const HostOut o{coef_out, css_ll_out, status_out, n_eval_out, n_grad_out, flags_out};
+    const FitOut o{coef_out, css_ll_out, status_out, n_eval_out, n_grad_out, flags_out};
     h->host_acc = arima_fit_stats{};
     // every context the call uses: settle what an earlier call left in it, then size its buffers for the largest chunk
     for (int j = 0; j < used; ++j) {
@@ -1389,10 +1225,8 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
                                          hipMemcpyHostToDevice, s));
             d_ui = c.d_uinit.as<double>();
         }
-        rc = fit_device_locked(h, c, ci, used, c.d_series.as<double>(), n, T, T, p, d, q, I, method, d_ui,
-                               c.d_coef.as<double>(), c.d_ll.as<double>(), c.d_status.as<int32_t>(),
-                               c.d_neval.as<int32_t>(), c.d_ngrad.as<int32_t>(), c.d_flags.as<uint8_t>(), s,
-                               nchunks > 1);
+        rc = fit_device_locked(h, c, c.rec, used, c.d_series.as<double>(), n, T, T, p, d, q, I, method, d_ui,
+                               c.dev_out(), s, nchunks > 1);
         if (rc == ARIMA_OK) {
             size_t off[6];
             pin_layout(n, k, off);
@@ -1413,7 +1247,6 @@ int arima_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
         if (rc == ARIMA_OK) rc = r;
     }
     h->stats = h->host_acc;
-    h->stats_ctx = -1;
     const int rf = take_fault(h);          // already reported per chunk when set: clear the sticky record
     return rc != ARIMA_OK ? rc : rf;
 }
@@ -1805,8 +1638,10 @@ int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_ser
 // ---------------------------------------------------------------------------------------------------------
 // order search over (d, p, q, intercept) — SURVEY.md 8(f) row 2 (config C5)
 // ---------------------------------------------------------------------------------------------------------
-// stream s waits for everything the first L search lanes have been given so far
-static void join_lanes_into(arima_handle *h, hipStream_t s, int L) {
+// Stream s waits for everything the first L search lanes have been given so far. The entry points join every lane,
+// also after an error part-way through the grid: later calls then wait for the lanes' reads of the search
+// workspaces through h->ev_done.
+static void join_lanes(arima_handle *h, hipStream_t s, int L = kMaxSearchLanes) {
     for (int j = 0; j < L; ++j) {
         SearchLane &ln = h->lanes[j];
         if (!ln.stream) continue;
@@ -1821,7 +1656,7 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         return set_err(h, ARIMA_E_INVALID_ARG, "bad search bounds");
     if (max_p > 5 || max_q > 5 || max_d > kMaxD) return set_err(h, ARIMA_E_UNSUPPORTED, "p, q <= 5, d <= 16");
     if (N < 0 || T < 0 || ld < T || !d_order || !d_coef || !d_aic) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    h->stats_ctx = -1;
+    h->stats_from = StatsFrom::kNone;
     h->stats = arima_fit_stats{};
     if (N == 0) return ARIMA_OK;
     HIPCHK(h, hipSetDevice(h->device));
@@ -1848,20 +1683,16 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         }
         // every workspace at its largest size before anything is enqueued: a growing DevBuf frees (hipFree
         // synchronises the device) and would serialise the host loop below with the fits already in flight
-        int rc = ARIMA_OK;
-        for (DevBuf *b : {&ln.coef, &ln.ws.init})
-            if (rc == ARIMA_OK) rc = b->ensure((size_t)N * 11 * sizeof(double));
+        int rc = ln.ws.reserve(N, 11);
+        if (rc == ARIMA_OK) rc = ln.coef.ensure((size_t)N * 11 * sizeof(double));
         if (rc == ARIMA_OK) rc = ln.ll.ensure((size_t)N * sizeof(double));
-        for (DevBuf *b : {&ln.status, &ln.neval, &ln.ngrad, &ln.ws.hr_status})
+        for (DevBuf *b : {&ln.status, &ln.neval, &ln.ngrad})
             if (rc == ARIMA_OK) rc = b->ensure((size_t)N * sizeof(int32_t));
         if (rc == ARIMA_OK) rc = ln.flags.ensure((size_t)N);
         if (rc == ARIMA_OK) rc = ln.best_aic.ensure((size_t)N * sizeof(double));
         if (rc == ARIMA_OK) rc = ln.best_order.ensure((size_t)N * 4 * sizeof(int32_t));
         if (rc == ARIMA_OK) rc = ln.best_coef.ensure((size_t)N * 11 * sizeof(double));
-        if (rc == ARIMA_OK) rc = ln.ws.ctl.ensure(kCtlWords * sizeof(unsigned long long));
         if (rc == ARIMA_OK) rc = ln.acc.ensure((kCtlWords + 1) * sizeof(unsigned long long));
-        if (rc == ARIMA_OK) rc = ln.ws.xring.ensure(sts::kExpressRingBytes);
-        if (rc == ARIMA_OK) rc = ln.ws.xready.ensure(sts::kExpressReadyBytes);
         if (rc != ARIMA_OK) {
             if (j == 0) return set_err(h, rc, "order search workspace");
             break;                                 // fewer lanes instead of failing the call
@@ -1922,10 +1753,14 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         for (size_t g = 0; g < grid.size(); ++g) plan[g % L].push_back((int)g);
     }
     int64_t fits = 0;
+    FitOpts lane_opt;
+    lane_opt.shared_gpu = L > 1;
+    if (L > 1) lane_opt.express_cus = h->search_express_blocks;
+    lane_opt.search = true;
     // the shared differenced copy: the fits of one d at a time (plan order is d-major on every lane)
     for (int dd = 0; dd <= (per_d ? 0 : max_d); ++dd) {
         if (!per_d) {
-            if (dd > 0) join_lanes_into(h, s, L);   // every fit of d - 1 has read the copy
+            if (dd > 0) join_lanes(h, s, L);        // every fit of d - 1 has read the copy
             RCCHK(h, diff_into(dd, h->os_diff[0]), "difference");
         }
         for (int j = 0; j < L; ++j) {
@@ -1941,10 +1776,8 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
                 // ARIMA(0,d,0) without intercept has no parameters: the reference throws (NoDataException);
                 // fit_kernels reports it per series and the select step skips it.
                 int64_t gridb = 0, xb = 0;
-                RCCHK(h, fit_kernels(h, ln.ws, dbuf.as<double>(), ldn, n, N, p, q, I, method, nullptr,
-                                     ln.coef.as<double>(), ln.ll.as<double>(), ln.status.as<int32_t>(),
-                                     ln.neval.as<int32_t>(), ln.ngrad.as<int32_t>(), ln.flags.as<uint8_t>(), ln.stream,
-                                     nullptr, &gridb, &xb, L > 1, L > 1 ? h->search_express_blocks : -2, true), "fit");
+                RCCHK(h, fit_kernels(h, ln.ws, dbuf.as<double>(), ldn, n, N, p, q, I, method, nullptr, ln.out(),
+                                     ln.stream, &gridb, &xb, lane_opt), "fit");
                 if (gridb > 0) {
                     h->last_grid = gridb;
                     h->last_express = xb;
@@ -1965,7 +1798,7 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
             }
         }
     }
-    join_lanes_into(h, s, L);
+    join_lanes(h, s, L);
     sts::SearchBests bests{};
     for (int j = 0; j < L; ++j) {
         bests.aic[j] = h->lanes[j].best_aic.as<double>();
@@ -1978,21 +1811,12 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         HIPCHK(h, hipMemcpyAsync(h->search_acc_host + (size_t)j * (kCtlWords + 1), h->lanes[j].acc.ptr,
                                  (kCtlWords + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIPCHK(h, hipEventRecord(h->ev[4], s));
-    h->stats_ctx = -3;
+    h->stats_from = StatsFrom::kSearch;
     h->search_lanes_used = L;
     h->search_n = N;
     h->search_fits = fits;
     if (n_fits) *n_fits = fits;
     return ARIMA_OK;
-}
-
-// The call's stream waits for everything its lanes have been given (also after an error part-way through the grid,
-// ADVICE r2): later calls then wait for the lanes' reads of the search workspaces through h->ev_done.
-static void join_lanes(arima_handle *h, hipStream_t s) {
-    for (auto &ln : h->lanes) {
-        if (!ln.stream) continue;
-        if (hipEventRecord(ln.ev_fit, ln.stream) == hipSuccess) hipStreamWaitEvent(s, ln.ev_fit, 0);
-    }
 }
 
 // Blocking entry points: the fault record covers the lanes' fit kernels (a dropped series must not
@@ -2004,11 +1828,7 @@ static int take_fault(arima_handle *h) {
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipMemcpyAsync(f, rec + 8, sizeof f, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (f[0] == 0) return ARIMA_OK;
-    char msg[160];
-    snprintf(msg, sizeof msg, "fit kernel watchdog fault %llu (info %llu %llu %llu %llu %llu)", f[0], f[1], f[2],
-             f[3], f[4], f[5]);
-    return set_err(h, ARIMA_E_DEVICE, msg);
+    return f[0] == 0 ? ARIMA_OK : report_fault(h, f);
 }
 
 int arima_order_search_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
@@ -2082,18 +1902,17 @@ static int autofit_slice(arima_handle *h, const double *d_series, int64_t N, int
         return set_err(h, ARIMA_E_OOM, "pinned");
     if (!h->ev_af) HIPCHK(h, hipEventCreateWithFlags(&h->ev_af, hipEventDisableTiming));
     const int P = std::min(kAfContexts, kMaxPipeline);
-    for (int j = 0; j < P; ++j) {                  // every context's gather buffer and fit workspace at full size
-        FitCtx &c = h->fctx[j];
-        RCCHK(h, c.diff.ensure((size_t)N * ldT * sizeof(double)), "autofit workspace");
-        RCCHK(h, c.ws.init.ensure((size_t)N * 11 * sizeof(double)), "workspace");
-        RCCHK(h, c.ws.hr_status.ensure((size_t)N * sizeof(int32_t)), "workspace");
-        RCCHK(h, c.ws.ctl.ensure(kCtlWords * sizeof(unsigned long long)), "workspace");
-        RCCHK(h, c.ws.xring.ensure(sts::kExpressRingBytes), "workspace");
-        RCCHK(h, c.ws.xready.ensure(sts::kExpressReadyBytes), "workspace");
-        if (c.has_done) HIPCHK(h, hipStreamWaitEvent(s, c.ev_done, 0));
-    }
+    // every context's gather buffer and fit workspace at full size
+    RCCHK(h, reserve_fit_ws(h, P, N, ldT, 11), "autofit workspace");
+    for (int j = 0; j < P; ++j)
+        if (h->fctx[j].has_done) HIPCHK(h, hipStreamWaitEvent(s, h->fctx[j].ev_done, 0));
+    // the round's results, one row per candidate fit (coefficient rows of 11 doubles; no evaluation counts)
+    const FitOut af{h->af_coef.as<double>(), h->af_ll.as<double>(), h->af_status.as<int32_t>(), nullptr, nullptr,
+                    h->af_flags.as<uint8_t>()};
+    FitOpts af_opt;
+    af_opt.shared_gpu = P > 1;
     // (1) d: the first of 0..max_d whose differencesOfOrderD(ts, d) passes kpsstest(_, "c") (ARIMA.scala:287-297)
-    const int32_t kpss_st = T <= 0 ? ARIMA_ST_NO_DATA : (T < 2 ? ARIMA_ST_NOT_ENOUGH_DATA : ARIMA_ST_OK);
+    const int32_t kpss_st = kpss_shape_status(T);
     int32_t *dsel = h->af_dsel.as<int32_t>();
     HIPCHK(h, hipMemsetAsync(dsel, 0xff, (size_t)N * sizeof(int32_t), s));
     if (kpss_st == ARIMA_ST_OK) {
@@ -2141,9 +1960,7 @@ static int autofit_slice(arima_handle *h, const double *d_series, int64_t N, int
             // fitModel(p, 0, q, diffedTs, intercept, "css-cgd") (:316); rows of order cb from off[cb] (coef stride k);
             // p > 5: the runtime-order path (fit_kernels dispatches it)
             RCCHK(h, fit_kernels(h, c.ws, c.diff.as<double>(), ldT, T, cnt, p, q, I, ARIMA_METHOD_CSS_CGD, nullptr,
-                                 h->af_coef.as<double>() + off[cb] * 11, h->af_ll.as<double>() + off[cb],
-                                 h->af_status.as<int32_t>() + off[cb], nullptr, nullptr,
-                                 h->af_flags.as<uint8_t>() + off[cb], c.stream, nullptr, &gridb, &xb, P > 1), "fit");
+                                 af.at(off[cb], 11), c.stream, &gridb, &xb, af_opt), "fit");
             // the Hannan-Rissanen inits and their status, kept for the round's css-bobyqa retries (below)
             const int k = p + q + I;
             if (!(p > 0 && q == 0) && k > 0) {
@@ -2179,9 +1996,7 @@ static int autofit_slice(arima_handle *h, const double *d_series, int64_t N, int
                                                   h->af_off.as<int64_t>(), ncombos, 11,
                                                   h->af_rlist.as<int32_t>() + (int64_t)k * rows_max,
                                                   h->af_rcount.as<unsigned>(), (int64_t)retries[k],
-                                                  h->af_init.as<double>(), h->af_hrst.as<int32_t>(),
-                                                  h->af_coef.as<double>(), h->af_ll.as<double>(),
-                                                  h->af_status.as<int32_t>(), h->af_flags.as<uint8_t>(),
+                                                  h->af_init.as<double>(), h->af_hrst.as<int32_t>(), af,
                                                   h->bobyqa_wave != 0, c.stream), "bobyqa refit");
             HIPCHK(h, end_fit(c, c.stream));
             ++launched;
@@ -2210,7 +2025,7 @@ static int autofit_locked(arima_handle *h, const double *d_series, int64_t N, in
     if (N < 0 || T < 0 || ld < T || (N > 0 && (!d_series || !d_order || !d_coef || !d_aic || !d_status)))
         return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     h->stats = arima_fit_stats{};
-    h->stats_ctx = -1;
+    h->stats_from = StatsFrom::kNone;
     if (N == 0) return ARIMA_OK;
     HIPCHK(h, hipSetDevice(h->device));
     const int64_t ldT = row_stride(h, T);
@@ -2280,7 +2095,7 @@ int arima_kpss_batch(arima_handle *h, const double *series, int64_t N, int32_t T
     CallFrame f(h, kHostBuffers);
     if (N == 0) return ARIMA_OK;
     if (!series || !stat_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int32_t st = T <= 0 ? ARIMA_ST_NO_DATA : (T < 2 ? ARIMA_ST_NOT_ENOUGH_DATA : ARIMA_ST_OK);
+    const int32_t st = kpss_shape_status(T);
     PASSCHK(f.begin());
     if (st == ARIMA_ST_OK) {
         int64_t ld = 0;
