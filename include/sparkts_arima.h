@@ -370,7 +370,61 @@ int arima_garch_remove_effects_batch_device(arima_handle *h, const double *d_ser
 int arima_garch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
                                          int64_t ld, const double *d_coef, double *d_out, int64_t ld_out,
                                          void *stream);
-/* Counters of the last EWMA / GARCH fit call on the handle (waits for its device work). The fit kernel runs one wave
+/* ---- ARGARCH (GARCH.scala:56-70, 198-260), ARModel's pair (Autoregression.scala:56-96) and the GARCH samples ------ *
+ * The argument rules of the section above hold for every entry point here.
+ *
+ * ARGARCH.fitModel (GARCH.scala:63-69): Autoregression.fitModel(ts) -- AR(1) with an intercept, the arithmetic of
+ * arima_fit_batch(p = 1, d = 0, q = 0, intercept), bit for bit -- then GARCH.fitModel on the residuals
+ * r(0) = ts(0) - c, r(i) = (ts(i) - c) - ts(i - 1) * phi (ARModel.removeTimeDependentEffects). The residuals are formed
+ * inside the GARCH passes from the raw rows; no N x T residual buffer exists on the device.
+ * coef_out N x 5 = (c, phi, omega, alpha, beta); ll_out N: GARCHModel.logLikelihood of the residuals at the fitted
+ * parameters. status_out: the AR stage's status when it is not ARIMA_ST_OK (ARIMA_ST_NO_DATA at T = 1,
+ * _NOT_ENOUGH_DATA at T = 2, _SINGULAR for a constant row) with both counters 0, else the GARCH stage's. A series
+ * that failed in either stage has five NaN coefficients and a NaN ll (the reference throws and returns no model).  */
+int arima_argarch_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, double *coef_out,
+                            double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out);
+int arima_argarch_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                   double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                   int32_t *d_n_grad_out, void *stream);
+/* ARGARCHModel.removeTimeDependentEffects / addTimeDependentEffects (GARCH.scala:205-236); coef N x 5 */
+int arima_argarch_remove_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                       const double *coef, double *out);
+int arima_argarch_add_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                    const double *coef, double *out);
+int arima_argarch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                              int64_t ld, const double *d_coef, double *d_out, int64_t ld_out,
+                                              void *stream);
+int arima_argarch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                           int64_t ld, const double *d_coef, double *d_out, int64_t ld_out,
+                                           void *stream);
+/* ARModel.removeTimeDependentEffects / addTimeDependentEffects (Autoregression.scala:60-90) at order p; coef
+ * N x (1 + p) = (c, phi_1 .. phi_p) per series. Step i uses only the lags that exist (i - j - 1 >= 0), which differs
+ * from ARIMAModel's pair with d = q = 0. p < 1 returns ARIMA_E_INVALID_ARG, p > 20 ARIMA_E_UNSUPPORTED.
+ * ARModel.sample(n, rand) is add_effects of n gaussians (computed out of place it yields the same values).         */
+int arima_ar_remove_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, int32_t p,
+                                  const double *coef, double *out);
+int arima_ar_add_effects_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, int32_t p,
+                               const double *coef, double *out);
+int arima_ar_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                         int64_t ld, int32_t p, const double *d_coef, double *d_out, int64_t ld_out,
+                                         void *stream);
+int arima_ar_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                      int64_t ld, int32_t p, const double *d_coef, double *d_out, int64_t ld_out,
+                                      void *stream);
+/* GARCHModel.sample (GARCH.scala:164-185; coef N x 3) / ARGARCHModel.sample (:238-259; coef N x 5) with the gaussians
+ * drawn by the caller: z N x T, z(i, t) = the t-th nextGaussian() of series i; out N x T. As in the reference out(i, 0)
+ * is 0.0 and z(i, 0) only feeds the variance of step 1. N == 0 or T == 0 writes nothing.                            */
+int arima_garch_sample_batch(arima_handle *h, const double *z, int64_t n_series, int32_t T, const double *coef,
+                             double *out);
+int arima_argarch_sample_batch(arima_handle *h, const double *z, int64_t n_series, int32_t T, const double *coef,
+                               double *out);
+int arima_garch_sample_batch_device(arima_handle *h, const double *d_z, int64_t n_series, int32_t T, int64_t ld,
+                                    const double *d_coef, double *d_out, int64_t ld_out, void *stream);
+int arima_argarch_sample_batch_device(arima_handle *h, const double *d_z, int64_t n_series, int32_t T, int64_t ld,
+                                      const double *d_coef, double *d_out, int64_t ld_out, void *stream);
+
+/* Counters of the last EWMA / GARCH / ARGARCH fit call on the handle (waits for its device work; ARGARCH: its GARCH
+ * stage, whose rounds equal those of a GARCH fit of the residual rows). The fit kernel runs one wave
  * per 64 series in rounds: one joint objective + gradient pass over the wave's rows per round, finished lanes masked. */
 typedef struct arima_model_fit_stats {
     int64_t n_series;

@@ -162,3 +162,31 @@ MODEL_EFFECTS_FN(ewmaRemoveEffectsBatch, arima_ewma_remove_effects_batch)
 MODEL_EFFECTS_FN(ewmaAddEffectsBatch, arima_ewma_add_effects_batch)
 MODEL_EFFECTS_FN(garchRemoveEffectsBatch, arima_garch_remove_effects_batch)
 MODEL_EFFECTS_FN(garchAddEffectsBatch, arima_garch_add_effects_batch)
+
+/* arima_argarch_fit_batch (ARGARCH.fitModel, GARCH.scala:63-69): series N x T; coef N x 5 (c, phi, omega, alpha,
+ * beta), ll N, status N, nEval / nGrad N or null */
+JNIEXPORT jint JNICALL JNI_FN(argarchFitBatch)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,
+                                               jobject coef, jobject ll, jobject status, jobject nEval, jobject nGrad) {
+    (void)self;
+    return arima_argarch_fit_batch((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t,
+                                   (double *)BUF(env, coef), (double *)BUF(env, ll), (int32_t *)BUF(env, status),
+                                   (int32_t *)BUF(env, nEval), (int32_t *)BUF(env, nGrad));
+}
+
+/* ARGARCHModel's pair (GARCH.scala:205-236; coef N x 5) and GARCHModel.sample / ARGARCHModel.sample (:164-185,
+ * :238-259) from the caller's gaussians z N x T (coef N x 3 / N x 5): out N x T (out may not overlap an input) */
+MODEL_EFFECTS_FN(argarchRemoveEffectsBatch, arima_argarch_remove_effects_batch)
+MODEL_EFFECTS_FN(argarchAddEffectsBatch, arima_argarch_add_effects_batch)
+MODEL_EFFECTS_FN(garchSampleBatch, arima_garch_sample_batch)
+MODEL_EFFECTS_FN(argarchSampleBatch, arima_argarch_sample_batch)
+
+/* ARModel's pair (Autoregression.scala:60-90) at order p: series N x T, coef N x (1 + p) = (c, phi_1 .. phi_p) */
+#define AR_EFFECTS_FN(jname, cname)                                                                                \
+    JNIEXPORT jint JNICALL JNI_FN(jname)(JNIEnv *env, jobject self, jlong h, jobject series, jlong n, jint t,      \
+                                         jint p, jobject coef, jobject out) {                                      \
+        (void)self;                                                                                                \
+        return cname((arima_handle *)(intptr_t)h, (const double *)BUF(env, series), n, t, p,                       \
+                     (const double *)BUF(env, coef), (double *)BUF(env, out));                                     \
+    }
+AR_EFFECTS_FN(arRemoveEffectsBatch, arima_ar_remove_effects_batch)
+AR_EFFECTS_FN(arAddEffectsBatch, arima_ar_add_effects_batch)

@@ -31,7 +31,8 @@ import org.apache.commons.math3.exception.{MathIllegalArgumentException, NoDataE
   NumberIsTooLargeException, TooManyEvaluationsException, TooManyIterationsException}
 import org.apache.commons.math3.exception.util.LocalizedFormats
 import org.apache.commons.math3.linear.SingularMatrixException
-import org.apache.spark.mllib.linalg.{Vector, Vectors}
+import org.apache.commons.math3.random.RandomGenerator
+import org.apache.spark.mllib.linalg.{DenseVector, Vector, Vectors}
 import org.apache.spark.rdd.RDD
 
 /** JNI entry points (integration/jvm/native/sparkts_arima_jni.c -> include/sparkts_arima.h). */
@@ -75,6 +76,22 @@ object ArimaMI355XNative {
                                       out: DoubleBuffer): Int
   @native def garchAddEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
                                    out: DoubleBuffer): Int
+  // ARGARCH (GARCH.scala:56-70, 198-260): coef N x 5 = (c, phi, omega, alpha, beta); the samples take the gaussians z
+  @native def argarchFitBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                              ll: DoubleBuffer, status: IntBuffer, nEval: IntBuffer, nGrad: IntBuffer): Int
+  @native def argarchRemoveEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                                        out: DoubleBuffer): Int
+  @native def argarchAddEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                                     out: DoubleBuffer): Int
+  @native def garchSampleBatch(handle: Long, z: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                               out: DoubleBuffer): Int
+  @native def argarchSampleBatch(handle: Long, z: DoubleBuffer, n: Long, t: Int, coef: DoubleBuffer,
+                                 out: DoubleBuffer): Int
+  // ARModel's pair (Autoregression.scala:60-90): coef N x (1 + p) = (c, phi_1 .. phi_p)
+  @native def arRemoveEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, p: Int, coef: DoubleBuffer,
+                                   out: DoubleBuffer): Int
+  @native def arAddEffectsBatch(handle: Long, series: DoubleBuffer, n: Long, t: Int, p: Int, coef: DoubleBuffer,
+                                out: DoubleBuffer): Int
 }
 
 /** Per-series status codes of include/sparkts_arima.h, mapped back to the exception the reference throws. */
@@ -419,4 +436,67 @@ object ArimaMI355X {
     modelEffectsMany(values, Array(model.omega, model.alpha, model.beta), "arima_garch_add_effects_batch") {
       (rows, n, t, par, out) => ArimaMI355XNative.garchAddEffectsBatch(handle, rows, n, t, par, out)
     }
+
+  // ---- ARGARCH, ARModel's pair and the samples (GARCH.scala:56-70, 164-185, 198-260; Autoregression.scala:56-96) -----
+  /** One ABI call (arima_argarch_fit_batch): ARGARCH.fitModel of every row; params = (c, phi, omega, alpha, beta),
+    * objective = GARCHModel.logLikelihood of the AR residuals. The residuals never exist as a buffer. */
+  def argarchFitMany(values: Array[Array[Double]]): ModelFitResult =
+    modelFitMany(values, 5, "arima_argarch_fit_batch") { (rows, n, t, par, obj, st, ne, ng) =>
+      ArimaMI355XNative.argarchFitBatch(handle, rows, n, t, par, obj, st, ne, ng)
+    }
+
+  /** Drop-in for ARGARCH.fitModel (GARCH.scala:63-69): a batch of one, either stage's exception. */
+  def argarchFitModel(ts: Vector): ARGARCHModel = {
+    val r = argarchFitMany(Array(ts.toArray))
+    if (r.status(0) != ArimaStatus.OK) throw ArimaStatus.toException(r.status(0))
+    val p = r.params(0)
+    new ARGARCHModel(p(0), p(1), p(2), p(3), p(4))
+  }
+
+  private def coefOf(m: ARGARCHModel): Array[Double] = Array(m.c, m.phi, m.omega, m.alpha, m.beta)
+
+  /** Batched ARGARCHModel.removeTimeDependentEffects / addTimeDependentEffects (GARCH.scala:205-236). */
+  def removeTimeDependentEffectsMany(model: ARGARCHModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, coefOf(model), "arima_argarch_remove_effects_batch") { (rows, n, t, par, out) =>
+      ArimaMI355XNative.argarchRemoveEffectsBatch(handle, rows, n, t, par, out)
+    }
+
+  def addTimeDependentEffectsMany(model: ARGARCHModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, coefOf(model), "arima_argarch_add_effects_batch") { (rows, n, t, par, out) =>
+      ArimaMI355XNative.argarchAddEffectsBatch(handle, rows, n, t, par, out)
+    }
+
+  /** Batched ARModel.removeTimeDependentEffects / addTimeDependentEffects (Autoregression.scala:60-90). */
+  def removeTimeDependentEffectsMany(model: ARModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, model.c +: model.coefficients, "arima_ar_remove_effects_batch") {
+      (rows, n, t, par, out) =>
+        ArimaMI355XNative.arRemoveEffectsBatch(handle, rows, n, t, model.coefficients.length, par, out)
+    }
+
+  def addTimeDependentEffectsMany(model: ARModel, values: Array[Array[Double]]): Array[Array[Double]] =
+    modelEffectsMany(values, model.c +: model.coefficients, "arima_ar_add_effects_batch") {
+      (rows, n, t, par, out) =>
+        ArimaMI355XNative.arAddEffectsBatch(handle, rows, n, t, model.coefficients.length, par, out)
+    }
+
+  /** n gaussians from `rand`, in the order the reference's sample loops draw them. */
+  private def gaussians(n: Int, rand: RandomGenerator): Array[Double] = Array.fill(n)(rand.nextGaussian())
+
+  /** GARCHModel.sample(n, rand) (GARCH.scala:164-185): the draws are made here, in order, and the recursion runs on
+    * the device (arima_garch_sample_batch). */
+  def sample(model: GARCHModel, n: Int, rand: RandomGenerator): Array[Double] =
+    modelEffectsMany(Array(gaussians(n, rand)), Array(model.omega, model.alpha, model.beta),
+      "arima_garch_sample_batch") { (z, rows, t, par, out) =>
+      ArimaMI355XNative.garchSampleBatch(handle, z, rows, t, par, out)
+    }.head
+
+  /** ARGARCHModel.sample(n, rand) (GARCH.scala:238-259). */
+  def sample(model: ARGARCHModel, n: Int, rand: RandomGenerator): Array[Double] =
+    modelEffectsMany(Array(gaussians(n, rand)), coefOf(model), "arima_argarch_sample_batch") {
+      (z, rows, t, par, out) => ArimaMI355XNative.argarchSampleBatch(handle, z, rows, t, par, out)
+    }.head
+
+  /** ARModel.sample(n, rand) (Autoregression.scala:92-95): the model driven by n gaussians. */
+  def sample(model: ARModel, n: Int, rand: RandomGenerator): Vector =
+    new DenseVector(addTimeDependentEffectsMany(model, Array(gaussians(n, rand))).head)
 }

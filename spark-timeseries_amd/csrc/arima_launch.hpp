@@ -34,21 +34,30 @@ int launch_effects(const double *in, int64_t ld_in, const double *coef, int k, d
 constexpr int kDgW = 8;
 int launch_diag(const double *rows, int64_t ld, int64_t N, int T, int max_lag, double *acf_out, double *dw_out,
                 double *lb_stat_out, double *lb_pvalue_out, hipStream_t s);
-// ---- the small models: EWMA and GARCH(1,1) (arima_models.hip; cg_small.hpp, model_pass.hpp) ----
-// params / coef_out hold K doubles per series: EWMA (smoothing), GARCH (omega, alpha, beta)
-constexpr int kModelEwma = 0, kModelGarch = 1;
-inline int model_num_params(int model) { return model == kModelEwma ? 1 : 3; }
+// ---- the small models: EWMA, GARCH(1,1) and ARGARCH (arima_models.hip; cg_small.hpp, model_pass.hpp) ----
+// params / coef_out hold NP doubles per series: EWMA (smoothing), GARCH (omega, alpha, beta), ARGARCH (c, phi, omega,
+// alpha, beta)
+constexpr int kModelEwma = 0, kModelGarch = 1, kModelArGarch = 2;
+inline int model_num_params(int model) { return model == kModelEwma ? 1 : model == kModelGarch ? 3 : 5; }
 constexpr int kModelCtlWords = 3;  // k_model_fit's counters: wave passes, live lane-passes, the largest pass count of a wave
-// EWMA.fitModel / GARCH.fitModel of every row (T >= 1); n_eval_out, n_grad_out and ctl are optional
+// EWMA.fitModel / GARCH.fitModel of every row (T >= 1); n_eval_out, n_grad_out and ctl are optional.
+// kModelArGarch: the GARCH stage of ARGARCH.fitModel on the raw rows; aux (N x 2) = the AR stage's (c, phi) and
+// aux_status (N) its status (launch_ar_fit(p = 1, I = 1)'s coef and status), both required
 int launch_model_fit(int model, const double *rows, int64_t ld, int64_t N, int T, double *coef_out, double *obj_out,
                      int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out, unsigned long long *ctl,
-                     hipStream_t s);
+                     hipStream_t s, const double *aux = nullptr, const int32_t *aux_status = nullptr);
 // objective (f_out N) and gradient (g_out N x K, the reference's returned order) at params; either output optional
 int launch_model_eval(int model, const double *rows, int64_t ld, int64_t N, int T, const double *params, double *f_out,
                       double *g_out, hipStream_t s);
 // removeTimeDependentEffects (add == 0) / addTimeDependentEffects (add == 1); out may not overlap in
 int launch_model_effects(int model, const double *in, int64_t ld_in, const double *params, double *out, int64_t ld_out,
                          int64_t N, int T, int add, hipStream_t s);
+// ARModel's pair at order 1 <= p <= kGenMaxOrder; coef N x (1 + p) = (c, phi_1 .. phi_p); out may not overlap in
+int launch_ar_effects(const double *in, int64_t ld_in, const double *coef, int p, double *out, int64_t ld_out,
+                      int64_t N, int T, int add, hipStream_t s);
+// GARCHModel.sample (kModelGarch) / ARGARCHModel.sample (kModelArGarch) from the caller's standard normals z
+int launch_garch_sample(int model, const double *z, int64_t ld_in, const double *params, double *out, int64_t ld_out,
+                        int64_t N, int T, hipStream_t s);
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.

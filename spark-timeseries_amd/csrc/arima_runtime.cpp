@@ -279,7 +279,8 @@ struct arima_handle {
     DevBuf dg_resid;
     // the small models (EWMA, GARCH): the fit kernel's counters of the last fit
     DevBuf md_ctl;
-    int64_t md_last_n = -1;        // series of the last EWMA / GARCH fit (-1: none yet)
+    int64_t md_last_n = -1;        // series of the last EWMA / GARCH / ARGARCH fit (-1: none yet)
+    DevBuf md_ar;                  // ARGARCH's AR stage per series: (c, phi), its CSS log-likelihood, its status
 };
 
 namespace {
@@ -2124,15 +2125,29 @@ int arima_sample_batch_device(arima_handle *h, double *d_series, int64_t N, int3
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// the small models: EWMA and GARCH(1,1) (arima_models.hip) -- fits, objective / gradient, the TimeSeriesModel pairs
+// the small models: EWMA, GARCH(1,1) and ARGARCH (arima_models.hip) -- fits, objective / gradient, the TimeSeriesModel
+// pairs (ARModel's too) and the sample recursions
 // ---------------------------------------------------------------------------------------------------------
 namespace {
 int md_fit_launch(arima_handle *h, int model, const double *rows, int64_t ld, int64_t N, int T, double *coef,
                   double *obj, int32_t *status, int32_t *n_eval, int32_t *n_grad, hipStream_t s) {
     RCCHK(h, h->md_ctl.ensure(sts::kModelCtlWords * sizeof(unsigned long long)), "counters");
     HIPCHK(h, hipMemsetAsync(h->md_ctl.ptr, 0, sts::kModelCtlWords * sizeof(unsigned long long), s));
+    const double *aux = nullptr;
+    const int32_t *aux_status = nullptr;
+    if (model == sts::kModelArGarch) {
+        // ARGARCH.fitModel's first stage, Autoregression.fitModel(ts): the kernel arima_fit_batch(1, 0, 0, intercept)
+        // runs, into an N x 2 workspace. The GARCH stage reads (c, phi) from it and forms the residuals in its passes.
+        RCCHK(h, h->md_ar.ensure((size_t)N * (3 * sizeof(double) + sizeof(int32_t))), "AR workspace");
+        double *ar_coef = h->md_ar.as<double>(), *ar_ll = ar_coef + 2 * N;
+        int32_t *ar_status = reinterpret_cast<int32_t *>(ar_ll + N);
+        RCCHK(h, sts::launch_ar_fit(rows, ld, T, N, 1, 1, sts::FitOut{ar_coef, ar_ll, ar_status, nullptr, nullptr, nullptr},
+                                    s), "ar fit");
+        aux = ar_coef;
+        aux_status = ar_status;
+    }
     RCCHK(h, sts::launch_model_fit(model, rows, ld, N, T, coef, obj, status, n_eval, n_grad,
-                                   h->md_ctl.as<unsigned long long>(), s), "model fit");
+                                   h->md_ctl.as<unsigned long long>(), s, aux, aux_status), "model fit");
     h->md_last_n = N;
     return ARIMA_OK;
 }
@@ -2199,38 +2214,67 @@ int md_eval_host(arima_handle *h, int model, const double *series, int64_t N, in
     return f.finish();
 }
 
-int md_effects_host(arima_handle *h, int model, const double *in_rows, int64_t N, int32_t T, const double *params,
-                    double *out, int add) {
+// what a streaming call runs: a model's pair (add 0 / 1), ARModel's pair at order p, or a sample recursion
+enum { kFxPair = 0, kFxArPair = 1, kFxSample = 2 };
+struct FxKind {
+    int kind, model, p, add;
+    int num_params() const { return kind == kFxArPair ? 1 + p : sts::model_num_params(model); }
+};
+int fx_check(arima_handle *h, const FxKind &k) {
+    if (k.kind != kFxArPair) return ARIMA_OK;
+    if (k.p < 1) return set_err(h, ARIMA_E_INVALID_ARG, "AR order below 1");
+    if (k.p > sts::kGenMaxOrder) return set_err(h, ARIMA_E_UNSUPPORTED, "AR order above 20");
+    return ARIMA_OK;
+}
+int fx_launch(const FxKind &k, const double *in, int64_t ld_in, const double *params, double *out, int64_t ld_out,
+              int64_t N, int T, hipStream_t s) {
+    if (k.kind == kFxArPair) return sts::launch_ar_effects(in, ld_in, params, k.p, out, ld_out, N, T, k.add, s);
+    if (k.kind == kFxSample) return sts::launch_garch_sample(k.model, in, ld_in, params, out, ld_out, N, T, s);
+    return sts::launch_model_effects(k.model, in, ld_in, params, out, ld_out, N, T, k.add, s);
+}
+
+int fx_host(arima_handle *h, const FxKind &k, const double *in_rows, int64_t N, int32_t T, const double *params,
+                    double *out) {
     if (!h) return ARIMA_E_INVALID_ARG;
     CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    PASSCHK(fx_check(h, k));
     if (N == 0 || T == 0) return ARIMA_OK;
     if (!in_rows || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = sts::model_num_params(model);
+    const int K = k.num_params();
     const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
     RCCHK(h, check_overlap(h, {ByteSpan(in_rows, row_bytes), ByteSpan(params, par_bytes)}, {ByteSpan(out, row_bytes)}),
           "overlap");
     PASSCHK(f.begin());
     PASSCHK(f.stage({stage_in(in_rows, row_bytes), stage_in(params, par_bytes), stage_out(out, row_bytes)}));
-    RCCHK(h, sts::launch_model_effects(model, f.dev<double>(0), T, f.dev<double>(1), f.dev<double>(2), T, N, T, add,
-                                       f.s()), "model effects");
+    RCCHK(h, fx_launch(k, f.dev<double>(0), T, f.dev<double>(1), f.dev<double>(2), T, N, T, f.s()), "model effects");
     return f.finish();
 }
 
-int md_effects_device(arima_handle *h, int model, const double *d_in, int64_t N, int32_t T, int64_t ld,
-                      const double *d_params, double *d_out, int64_t ld_out, void *stream, int add) {
+int fx_device(arima_handle *h, const FxKind &k, const double *d_in, int64_t N, int32_t T, int64_t ld,
+                      const double *d_params, double *d_out, int64_t ld_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
     CallFrame f(h, kDeviceBuffers);
     if (N < 0 || T < 0 || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    PASSCHK(fx_check(h, k));
     if (N == 0 || T == 0) return ARIMA_OK;
     if (!d_in || !d_params || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = sts::model_num_params(model);
+    const int K = k.num_params();
     RCCHK(h, check_overlap(h, {ByteSpan(d_in, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
                                ByteSpan(d_params, N * K * (int64_t)sizeof(double))},
                            {ByteSpan(d_out, ((N - 1) * ld_out + T) * (int64_t)sizeof(double))}), "overlap");
     PASSCHK(f.begin(stream));
-    RCCHK(h, sts::launch_model_effects(model, d_in, ld, d_params, d_out, ld_out, N, T, add, f.s()), "model effects");
+    RCCHK(h, fx_launch(k, d_in, ld, d_params, d_out, ld_out, N, T, f.s()), "model effects");
     return f.finish();
+}
+// the pairs of EWMA / GARCH / ARGARCH
+int md_effects_host(arima_handle *h, int model, const double *in_rows, int64_t N, int32_t T, const double *params,
+                    double *out, int add) {
+    return fx_host(h, FxKind{kFxPair, model, 0, add}, in_rows, N, T, params, out);
+}
+int md_effects_device(arima_handle *h, int model, const double *d_in, int64_t N, int32_t T, int64_t ld,
+                      const double *d_params, double *d_out, int64_t ld_out, void *stream, int add) {
+    return fx_device(h, FxKind{kFxPair, model, 0, add}, d_in, N, T, ld, d_params, d_out, ld_out, stream);
 }
 }  // namespace
 
@@ -2318,11 +2362,82 @@ int arima_garch_add_effects_batch_device(arima_handle *h, const double *d_series
     return md_effects_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 1);
 }
 
+int arima_argarch_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *coef_out,
+                            double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
+    return md_fit_host(h, sts::kModelArGarch, series, N, T, coef_out, ll_out, status_out, n_eval_out, n_grad_out);
+}
+
+int arima_argarch_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                   double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                   int32_t *d_n_grad_out, void *stream) {
+    return md_fit_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
+                         d_n_grad_out, stream);
+}
+
+int arima_argarch_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                                       double *out) {
+    return md_effects_host(h, sts::kModelArGarch, series, N, T, coef, out, 0);
+}
+
+int arima_argarch_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
+                                    double *out) {
+    return md_effects_host(h, sts::kModelArGarch, series, N, T, coef, out, 1);
+}
+
+int arima_argarch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                              const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 0);
+}
+
+int arima_argarch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                           const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return md_effects_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 1);
+}
+
+int arima_ar_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
+                                  const double *coef, double *out) {
+    return fx_host(h, FxKind{kFxArPair, 0, p, 0}, series, N, T, coef, out);
+}
+
+int arima_ar_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
+                               const double *coef, double *out) {
+    return fx_host(h, FxKind{kFxArPair, 0, p, 1}, series, N, T, coef, out);
+}
+
+int arima_ar_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                         int32_t p, const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return fx_device(h, FxKind{kFxArPair, 0, p, 0}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
+}
+
+int arima_ar_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                      int32_t p, const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return fx_device(h, FxKind{kFxArPair, 0, p, 1}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
+}
+
+int arima_garch_sample_batch(arima_handle *h, const double *z, int64_t N, int32_t T, const double *coef, double *out) {
+    return fx_host(h, FxKind{kFxSample, sts::kModelGarch, 0, 0}, z, N, T, coef, out);
+}
+
+int arima_argarch_sample_batch(arima_handle *h, const double *z, int64_t N, int32_t T, const double *coef, double *out) {
+    return fx_host(h, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, z, N, T, coef, out);
+}
+
+int arima_garch_sample_batch_device(arima_handle *h, const double *d_z, int64_t N, int32_t T, int64_t ld,
+                                    const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return fx_device(h, FxKind{kFxSample, sts::kModelGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out, stream);
+}
+
+int arima_argarch_sample_batch_device(arima_handle *h, const double *d_z, int64_t N, int32_t T, int64_t ld,
+                                      const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
+    return fx_device(h, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out,
+                             stream);
+}
+
 int arima_get_last_model_fit_stats(arima_handle *h, arima_model_fit_stats *out) {
     if (!h || !out) return ARIMA_E_INVALID_ARG;
     std::lock_guard<std::mutex> lk(h->mu);
     memset(out, 0, sizeof *out);
-    if (h->md_last_n < 0) return set_err(h, ARIMA_E_INVALID_ARG, "no EWMA / GARCH fit on this handle yet");
+    if (h->md_last_n < 0) return set_err(h, ARIMA_E_INVALID_ARG, "no EWMA / GARCH / ARGARCH fit on this handle yet");
     HIPCHK(h, hipSetDevice(h->device));
     if (h->has_done) HIPCHK(h, hipEventSynchronize(h->ev_done));
     unsigned long long w[sts::kModelCtlWords];

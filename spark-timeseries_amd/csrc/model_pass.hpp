@@ -2,10 +2,17 @@
 // the joint objective + gradient pass of a fit and the TimeSeriesModel pair, for
 //   EWMA        EWMAModel.sse / gradient / removeTimeDependentEffects / addTimeDependentEffects   (EWMA.scala:81-143)
 //   GARCH(1,1)  GARCHModel.logLikelihood / gradient / iterateWithHAndEta / the pair               (GARCH.scala:82-162)
+//   ARGARCH     ARGARCH.fitModel's GARCH stage on the AR(1) residuals, ARGARCHModel's pair        (GARCH.scala:63-69, 205-236)
+//   AR(p)       ARModel's pair at a runtime order                                                 (Autoregression.scala:60-90)
+//   and the sample recursions of GARCHModel / ARGARCHModel driven by the caller's normals         (GARCH.scala:164-185, 238-259)
 // in the reference's operation order (every a * b + c is two operations: the library is built with -ffp-contract=off).
 // Nothing is special-cased: a negative h gives NaN through the log, overflow gives Inf, x / 0 is IEEE's.
 // Portable C++ (host and device): k_model_fit / k_model_eval / k_model_effects (arima_models.hip) and
-// tests/sim/smallfit_sim.cpp run the same code.
+// tests/sim/smallfit_sim.cpp and tests/sim/argarch_sim.cpp run the same code.
+//
+// A model has K parameters the optimizer moves and A auxiliary per-series constants it does not (Ewma, Garch: A = 0;
+// ArGarch: A = 2, the AR stage's (c, phi)). Pass::begin(x, aux) takes both; a parameter block of the pair (Fx::begin)
+// is the A constants followed by the K parameters, NP = A + K doubles.
 //
 // GARCH's gradient keeps the reference's order: GARCHModel.gradient RETURNS (alpha, beta, omega) halves (:114) while
 // GARCH.fitModel's parameters are (omega, alpha, beta) (:40-41), so the optimizer applies alpha's derivative to omega,
@@ -84,7 +91,7 @@ STS_SM_HD double sm_log(double x) {
 // EWMA: one parameter, `smoothing`; MINIMIZE sse from [.94]
 // ---------------------------------------------------------------------------------------------------------------
 struct Ewma {
-    static constexpr int K = 1;
+    static constexpr int K = 1, A = 0, NP = K + A;
     static constexpr bool kMinimize = true;                  // val goal = GoalType.MINIMIZE (EWMA.scala:64)
     STS_SM_HD static void initial_guess(double *x) { x[0] = .94; }
 
@@ -95,7 +102,7 @@ struct Ewma {
         double a, om;            // smoothing, 1 - smoothing
         double s, xp, ps;        // smoothed(t - 1), ts(t - 1), prevSmoothed
         double pd, dj, sq;       // prevDSda, dJda, sqrErrors
-        STS_SM_HD void begin(const double *x) {
+        STS_SM_HD void begin(const double *x, const double * = nullptr) {
             a = x[0];
             om = 1 - a;
             s = xp = ps = 0.0;
@@ -141,7 +148,7 @@ struct Ewma {
 // GARCH(1,1): parameters (omega, alpha, beta); no GoalType, so commons maximises logLikelihood from [.2, .2, .2]
 // ---------------------------------------------------------------------------------------------------------------
 struct Garch {
-    static constexpr int K = 3;
+    static constexpr int K = 3, A = 0, NP = K + A;
     static constexpr bool kMinimize = false;
     STS_SM_HD static void initial_guess(double *x) { x[0] = .2; x[1] = .2; x[2] = .2; }
 
@@ -151,7 +158,7 @@ struct Garch {
         double ph, xp;                   // prevH, ts(i - 1)
         double sum, og, ag, bg;          // the log-likelihood sum; omega / alpha / betaGradient
         double od, ad, bd;               // omega / alpha / betaDhdtheta
-        STS_SM_HD void begin(const double *x) {
+        STS_SM_HD void begin(const double *x, const double * = nullptr) {
             omega = x[0]; alpha = x[1]; beta = x[2];
             ph = omega / (1 - alpha - beta);
             xp = 0.0;
@@ -198,6 +205,113 @@ struct Garch {
             return o;
         }
     };
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// ARGARCH: AR(1) with an intercept, GARCH(1,1) errors. The optimizer's parameters are Garch's; (c, phi) come from the
+// AR stage (Autoregression.fitModel) and stay fixed, so the fit is Garch's on the residuals
+//   r(0) = ts(0) - c,  r(i) = (ts(i) - c) - ts(i - 1) * phi      (ARModel.removeTimeDependentEffects, p = 1)
+// formed per column from the raw row: two roundings, in that order. The residual row is never stored.
+// ---------------------------------------------------------------------------------------------------------------
+struct ArGarch {
+    static constexpr int K = 3, A = 2, NP = K + A;
+    static constexpr bool kMinimize = false;
+    STS_SM_HD static void initial_guess(double *x) { Garch::initial_guess(x); }
+
+    struct Pass {
+        Garch::Pass g;
+        double c, phi, pv;               // pv: ts(t - 1), the raw value
+        STS_SM_HD void begin(const double *x, const double *aux) {
+            g.begin(x);
+            c = aux[0]; phi = aux[1];
+            pv = 0.0;
+        }
+        STS_SM_HD void step(int t, double v) {
+            double r = v - c;
+            if (t > 0) r = r - pv * phi;
+            pv = v;
+            g.step(t, r);
+        }
+        STS_SM_HD void end(int T, double *f, double *gr) const { g.end(T, f, gr); }
+    };
+
+    // ARGARCHModel.removeTimeDependentEffects (:205-219) / addTimeDependentEffects (:221-236; recursion on dest(i - 1));
+    // x = (c, phi, omega, alpha, beta)
+    template <bool ADD>
+    struct Fx {
+        double c, phi, omega, alpha, beta, pe, pv, pr;       // prevEta, prevVariance; pr: ts(i - 1) / dest(i - 1)
+        STS_SM_HD void begin(const double *x) {
+            c = x[0]; phi = x[1]; omega = x[2]; alpha = x[3]; beta = x[4];
+            pv = omega / (1.0 - alpha - beta);
+            pe = pr = 0.0;
+        }
+        STS_SM_HD double step(int t, double v) {
+            if (t > 0) pv = omega + alpha * pe * pe + beta * pv;
+            const double sd = __builtin_sqrt(pv);
+            double o;
+            if (ADD) {
+                pe = v * sd;
+                o = t > 0 ? c + phi * pr + pe : c + pe;
+                pr = o;
+            } else {
+                pe = t > 0 ? v - c - phi * pr : v - c;
+                o = pe / sd;
+                pr = v;
+            }
+            return o;
+        }
+    };
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// ARModel's pair at order p <= kArMaxP (Autoregression.scala:60-90): dest(i) = ts(i) - c (remove) or c + ts(i) (add),
+// then one lag at a time, j ascending, only the lags that exist (i - j - 1 >= 0). `coef` = (c, phi_1 .. phi_p).
+// hist (the caller's, p doubles: a runtime-indexed array belongs in LDS on the device, not in registers) is a ring of
+// the last p raw values (remove) or outputs (add): value t lives at hist[t % p].
+// ---------------------------------------------------------------------------------------------------------------
+constexpr int kArMaxP = 20;
+template <bool ADD>
+struct ArFx {
+    int p;
+    const double *coef;
+    double *hist;
+    STS_SM_HD void begin(const double *coef_, int p_, double *hist_) { coef = coef_; p = p_; hist = hist_; }
+    STS_SM_HD double step(int t, double v) {
+        double o = ADD ? coef[0] + v : v - coef[0];
+        const int lags = t < p ? t : p;
+        int k = t % p;                               // slot of value t; value t - j - 1 is j + 1 slots before it
+        const int slot = k;
+        for (int j = 0; j < lags; ++j) {
+            k = k == 0 ? p - 1 : k - 1;
+            o = ADD ? o + hist[k] * coef[1 + j] : o - hist[k] * coef[1 + j];
+        }
+        hist[slot] = ADD ? o : v;
+        return o;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// GARCHModel.sample / ARGARCHModel.sample (GARCH.scala:164-185, 238-259) with the gaussians pre-drawn: z(t) is the
+// t-th nextGaussian(). ts(0) is never assigned (0.0), z(0) only feeds variances(1); the variance recursion here is
+// omega + beta * v + alpha * eta * eta, not the pair's order. AR: x = (c, phi, omega, alpha, beta), else (omega, alpha, beta)
+// ---------------------------------------------------------------------------------------------------------------
+template <bool AR>
+struct GarchSample {
+    static constexpr int NP = AR ? 5 : 3;
+    double c, phi, omega, alpha, beta, var, eta, prev;
+    STS_SM_HD void begin(const double *x) {
+        c = AR ? x[0] : 0.0; phi = AR ? x[1] : 0.0;
+        omega = x[NP - 3]; alpha = x[NP - 2]; beta = x[NP - 1];
+        var = omega / (1 - alpha - beta);
+        eta = prev = 0.0;
+    }
+    STS_SM_HD double step(int t, double z) {
+        if (t > 0) var = omega + beta * var + alpha * eta * eta;
+        eta = __builtin_sqrt(var) * z;
+        if (t == 0) return 0.0;
+        prev = AR ? c + phi * prev + eta : eta;
+        return prev;
+    }
 };
 
 }  // namespace small

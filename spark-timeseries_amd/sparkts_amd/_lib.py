@@ -62,10 +62,16 @@ EXPORTED = [
     "arima_garch_add_effects_batch", "arima_ewma_remove_effects_batch_device", "arima_ewma_add_effects_batch_device",
     "arima_garch_remove_effects_batch_device", "arima_garch_add_effects_batch_device",
     "arima_get_last_model_fit_stats",
+    "arima_argarch_fit_batch", "arima_argarch_fit_batch_device", "arima_argarch_remove_effects_batch",
+    "arima_argarch_add_effects_batch", "arima_argarch_remove_effects_batch_device",
+    "arima_argarch_add_effects_batch_device", "arima_ar_remove_effects_batch", "arima_ar_add_effects_batch",
+    "arima_ar_remove_effects_batch_device", "arima_ar_add_effects_batch_device", "arima_garch_sample_batch",
+    "arima_argarch_sample_batch", "arima_garch_sample_batch_device", "arima_argarch_sample_batch_device",
 ]
 
-# the small models (EWMA.scala, GARCH.scala): parameters per series
-MODEL_PARAMS = {"ewma": 1, "garch": 3}
+# the small models (EWMA.scala, GARCH.scala): parameters per series; ARGARCH's are (c, phi, omega, alpha, beta)
+MODEL_PARAMS = {"ewma": 1, "garch": 3, "argarch": 5}
+AR_MAX_LAG = 20             # the library's order limit (ARModel's pair)
 
 
 class FitStats(ctypes.Structure):
@@ -180,7 +186,7 @@ def load():
                                                        _dp, _dp]
         L.arima_residual_diagnostics_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _i32, _i32, _i32, _i32, _vp,
                                                               _i32, _vp, _vp, _vp, _vp, _vp]
-        for m in ("ewma", "garch"):
+        for m in ("ewma", "garch", "argarch"):
             getattr(L, f"arima_{m}_fit_batch").argtypes = [H, _dp, _i64, _i32, _dp, _dp, _i32p, _i32p, _i32p]
             getattr(L, f"arima_{m}_fit_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
             for d in ("remove", "add"):
@@ -191,6 +197,13 @@ def load():
                    L.arima_garch_gradient_batch):
             fn.argtypes = [H, _dp, _i64, _i32, _dp, _dp]
         L.arima_get_last_model_fit_stats.argtypes = [H, ctypes.POINTER(ModelFitStats)]
+        for d in ("remove", "add"):
+            getattr(L, f"arima_ar_{d}_effects_batch").argtypes = [H, _dp, _i64, _i32, _i32, _dp, _dp]
+            getattr(L, f"arima_ar_{d}_effects_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _i32, _vp, _vp, _i64,
+                                                                        _vp]
+        for m in ("garch", "argarch"):
+            getattr(L, f"arima_{m}_sample_batch").argtypes = [H, _dp, _i64, _i32, _dp, _dp]
+            getattr(L, f"arima_{m}_sample_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
         _lib = L
         return L
 
@@ -455,8 +468,20 @@ class Engine:
         self._model_fit_device("garch", d_series, n_series, T, ld, d_coef, d_ll, d_status, d_n_eval, d_n_grad, stream,
                                blocking)
 
+    def argarch_fit_batch(self, series):
+        """ARGARCH.fitModel of every row (GARCH.scala:63-69): dict(coef N x 5 (c, phi, omega, alpha, beta), ll N, status,
+        n_eval, n_grad). The AR(1) residuals never exist as a buffer; a row that fails in either stage is all NaN."""
+        r = self._model_fit("argarch", series)
+        return dict(coef=r["coef"], ll=r["obj"], status=r["status"], n_eval=r["n_eval"], n_grad=r["n_grad"])
+
+    def argarch_fit_batch_device(self, d_series, n_series, T, ld, d_coef, d_ll, d_status, d_n_eval=None,
+                                 d_n_grad=None, stream=None, blocking=True):
+        """Device-pointer ARGARCH fits; d_coef N x 5 (c, phi, omega, alpha, beta)."""
+        self._model_fit_device("argarch", d_series, n_series, T, ld, d_coef, d_ll, d_status, d_n_eval, d_n_grad,
+                               stream, blocking)
+
     def model_fit_stats(self):
-        """Round counters of the last EWMA / GARCH fit (waits for it): n_series, wave_passes, lane_passes,
+        """Round counters of the last EWMA / GARCH / ARGARCH fit (waits for it): n_series, wave_passes, lane_passes,
         max_wave_passes."""
         s = ModelFitStats()
         self._check(self.L.arima_get_last_model_fit_stats(self.h, ctypes.byref(s)), "arima_get_last_model_fit_stats")
@@ -504,9 +529,60 @@ class Engine:
         """GARCHModel.addTimeDependentEffects (GARCH.scala:147-162): the model driven by the rows, (N, T)."""
         return self._model_call("arima_garch_add_effects_batch", "garch", series, coef, None)
 
+    def argarch_remove_effects(self, series, coef):
+        """ARGARCHModel.removeTimeDependentEffects (GARCH.scala:205-219); coef (5,) or (N, 5): (N, T)."""
+        return self._model_call("arima_argarch_remove_effects_batch", "argarch", series, coef, None)
+
+    def argarch_add_effects(self, series, coef):
+        """ARGARCHModel.addTimeDependentEffects (GARCH.scala:221-236), the recursion on dest(i - 1): (N, T)."""
+        return self._model_call("arima_argarch_add_effects_batch", "argarch", series, coef, None)
+
+    def garch_sample(self, z, coef):
+        """GARCHModel.sample (GARCH.scala:164-185) per row of standard normals z (row i, column t = the t-th
+        nextGaussian()); coef (3,) or (N, 3): (N, T) with column 0 equal to 0.0, as in the reference."""
+        return self._model_call("arima_garch_sample_batch", "garch", z, coef, None)
+
+    def argarch_sample(self, z, coef):
+        """ARGARCHModel.sample (GARCH.scala:238-259) per row of standard normals z; coef (5,) or (N, 5): (N, T)."""
+        return self._model_call("arima_argarch_sample_batch", "argarch", z, coef, None)
+
+    def _ar_effects(self, direction, series, p, coef):
+        series = self._rows(series)
+        N, T = series.shape
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64).reshape(-1, 1 + p), (N, 1 + p)))
+        out = np.empty((N, T))
+        name = f"arima_ar_{direction}_effects_batch"
+        self._check(getattr(self.L, name)(self.h, _ptr(series), N, T, p, _ptr(coef), _ptr(out)), name)
+        return out
+
+    def ar_remove_effects(self, series, p, coef):
+        """ARModel.removeTimeDependentEffects (Autoregression.scala:60-75) at order p; coef (1 + p,) or (N, 1 + p) =
+        (c, phi_1 .. phi_p): (N, T)."""
+        return self._ar_effects("remove", series, p, coef)
+
+    def ar_add_effects(self, series, p, coef):
+        """ARModel.addTimeDependentEffects (Autoregression.scala:77-90), the recursion on dest: (N, T). With rows of
+        standard normals this is ARModel.sample."""
+        return self._ar_effects("add", series, p, coef)
+
+    def ar_effects_device(self, direction, d_series, n_series, T, ld, p, d_coef, d_out, ld_out, stream=None,
+                          blocking=True):
+        """Device-pointer ARModel pair, direction "remove" / "add"; d_coef N x (1 + p); no overlap."""
+        name = f"arima_ar_{direction}_effects_batch_device"
+        self._check(getattr(self.L, name)(self.h, d_series, n_series, T, ld, p, d_coef, d_out, ld_out, stream), name)
+        if blocking:
+            self.synchronize()
+
+    def model_sample_device(self, model, d_z, n_series, T, ld, d_coef, d_out, ld_out, stream=None, blocking=True):
+        """Device-pointer sample of model "garch" / "argarch" from the normals at d_z; no overlap."""
+        name = f"arima_{model}_sample_batch_device"
+        self._check(getattr(self.L, name)(self.h, d_z, n_series, T, ld, d_coef, d_out, ld_out, stream), name)
+        if blocking:
+            self.synchronize()
+
     def model_effects_device(self, model, direction, d_series, n_series, T, ld, d_params, d_out, ld_out, stream=None,
                              blocking=True):
-        """Device-pointer TimeSeriesModel pair of model "ewma" / "garch", direction "remove" / "add" (ints = raw HBM
+        """Device-pointer TimeSeriesModel pair of model "ewma" / "garch" / "argarch", direction "remove" / "add" (ints = raw HBM
         addresses; d_params N x K; d_out may not overlap d_series)."""
         name = f"arima_{model}_{direction}_effects_batch_device"
         self._check(getattr(self.L, name)(self.h, d_series, n_series, T, ld, d_params, d_out, ld_out, stream), name)

@@ -4,7 +4,8 @@ GARCH(1,1): h_t = omega + alpha * eta_{t-1}^2 + beta * h_{t-1}. `fit_model` is G
 commons-math3's Fletcher-Reeves conjugate gradient from (.2, .2, .2) on GARCHModel.logLikelihood. Two properties of the
 reference are reproduced, not repaired, so that this is a drop-in: no GoalType is passed, which makes commons maximise;
 and GARCHModel.gradient returns (alpha, beta, omega) halves while the parameters are (omega, alpha, beta), so each
-parameter moves along another one's derivative. `sc` is accepted and ignored. `sample` is not provided.
+parameter moves along another one's derivative. `sc` is accepted and ignored. `sample` takes the gaussians
+from the caller (the reference draws them from a commons RandomGenerator).
 """
 import numpy as np
 
@@ -95,3 +96,8 @@ class GARCHModel:
     def add_time_dependent_effects(self, ts, dest_ts=None):
         """addTimeDependentEffects (GARCH.scala:147-162): the model driven by the standardised `ts`."""
         return self._apply(self._eng.garch_add_effects, ts, dest_ts)
+
+    def sample(self, z):
+        """sample(n, rand) (GARCH.scala:164-185) with the gaussians drawn by the caller: z[t] is the t-th
+        rand.nextGaussian(). As in the reference the first value is 0.0 and z[0] only feeds the next variance."""
+        return self._apply(self._eng.garch_sample, z, None)

@@ -1,3 +1,5 @@
 from . import ARIMA  # noqa: F401
 from . import EWMA  # noqa: F401
 from . import GARCH  # noqa: F401
+from . import ARGARCH  # noqa: F401
+from . import Autoregression  # noqa: F401

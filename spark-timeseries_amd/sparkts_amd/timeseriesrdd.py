@@ -9,6 +9,7 @@ reference would fail the Spark task); `with_status=True` also returns the ARIMA_
 """
 import numpy as np
 
+from .models import ARGARCH as _argarch
 from .models import ARIMA as _arima
 from .models import EWMA as _ewma
 from .models import GARCH as _garch
@@ -108,6 +109,15 @@ def fit_garch_partition(records, with_status=False, device=None):
     m.beta) })`: (key, [omega, alpha, beta]) in input order; NaNs for a failed fit."""
     def fit(batch, dev):
         r = _garch.fit_models(batch, device=dev)
+        return r.coefficients, r.status
+    return _fit_model_partition(fit, records, with_status, device)
+
+
+def fit_argarch_partition(records, with_status=False, device=None):
+    """Partition-level drop-in for `mapSeries(v => { val m = ARGARCH.fitModel(v); Vectors.dense(m.c, m.phi, m.omega,
+    m.alpha, m.beta) })`: (key, [c, phi, omega, alpha, beta]) in input order; NaNs for a failed fit."""
+    def fit(batch, dev):
+        r = _argarch.fit_models(batch, device=dev)
         return r.coefficients, r.status
     return _fit_model_partition(fit, records, with_status, device)
 
