@@ -15,17 +15,16 @@
 // delayed by g W steps: the first group takes it from the tile it already has, later groups stream a second tile.
 // A call of at most W lags runs an instance of its own whose W is the smallest of 1, 2, 4, kDgW that holds them.
 //
-// Memory path: k_effects' (arima_effects.hip): [64 series x CH steps] tiles, coalesced loads transposed through LDS,
-// the next tile prefetched into registers while this one is consumed. Register arrays are indexed by constants only:
-// the loops over the lags of a group are fully unrolled and predicated on wave-uniform conditions (the lag count of
-// the group and the step), and full tiles of full groups take a path with no predicates at all, whose ring rotates by
-// renaming over W unrolled steps.
+// Memory path: row_tile.hpp (RowTile<CH>::load and store). Register arrays are indexed by constants only: the loops
+// over the lags of a group are fully unrolled and predicated on wave-uniform conditions (the lag count of the group and
+// the step), and full tiles of full groups take an unpredicated path whose ring rotates by renaming over W steps.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/sparkts_arima.h"
 #include "arima_chisq.hpp"
 #include "arima_launch.hpp"
+#include "row_tile.hpp"
 
 namespace sts {
 
@@ -50,63 +49,35 @@ __global__ __launch_bounds__(kDgWave) __attribute__((amdgpu_waves_per_eu(MULTI ?
     const double *__restrict__ rows, int64_t ld, int64_t N, int T, int L, double *__restrict__ acf_out,
     double *__restrict__ dw_out, double *__restrict__ lb_stat_out, double *__restrict__ lb_pvalue_out) {
     static_assert(W == kDgW || (!MULTI && kDgW % W == 0), "group width");
-    constexpr int RPL = kDgWave / CH;                 // rows per coalesced load instruction
-    static_assert(kDgWave % CH == 0 && CH % W == 0 && CH >= W, "tile width");
-    __shared__ double tile[kDgWave][CH + 1];
+    using Tile = RowTile<CH>;                         // the memory path (row_tile.hpp)
+    static_assert(CH % W == 0 && CH >= W, "tile width");
+    __shared__ typename Tile::Lds tile;
     __shared__ double tile2[MULTI ? kDgWave : 1][CH + 1];
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kDgWave;
     const int64_t sid = row0 + lane;
     const bool live = sid < N;
-    const int tu = lane % CH, tr = lane / CH;
     const int64_t Tl = T;
 
-    // tile loads: lane reads element tu of row j * RPL + tr. One base address and a uniform stride, so no per-row
-    // address lives across the pass; the column is clamped (columns outside [0, T) are never consumed) and the rows
-    // past N of the last workgroup are not loaded at all
     const int nrows = (int)(N - row0 < kDgWave ? N - row0 : kDgWave);
-    const int64_t jstride = (int64_t)RPL * ld;
-    double pf[CH], pf2[MULTI ? CH : 1];
-#pragma unroll
-    for (int j = 0; j < CH; ++j) pf[j] = 0.0;
-#pragma unroll
-    for (int j = 0; j < (MULTI ? CH : 1); ++j) pf2[j] = 0.0;
-    auto load_into = [&](double (&dst)[CH], int64_t t) {
-        const double *src = rows + (row0 + tr) * ld + t;
-        // keeps the CH row addresses from being formed once and held (128 registers) across the passes: they are
-        // rebuilt from this one pointer, one add each, at every tile
-        asm volatile("" : "+v"(src));
-        if (nrows == kDgWave) {
-#pragma unroll
-            for (int j = 0; j < CH; ++j) dst[j] = src[j * jstride];
-        } else {
-#pragma unroll
-            for (int j = 0; j < CH; ++j)
-                if (tr < nrows - j * RPL) dst[j] = src[j * jstride];
-        }
-    };
-    auto load_tile = [&](int64_t cb) { load_into(pf, cb + tu < Tl ? cb + tu : Tl - 1); };
-    auto load_tile2 = [&](int64_t cb) {               // the row delayed: columns before 0 are never consumed
-        const int64_t t = cb + tu < Tl ? cb + tu : Tl - 1;
-        if constexpr (MULTI) load_into(pf2, t < 0 ? 0 : t);
-    };
-    // one streaming pass over columns [cb0, T); `two`: also the tile delayed by b columns. body(cb, n): the lane's
-    // row is tile[lane][0 .. n), columns cb .. cb + n
+    const unsigned long long mask = Tile::rows_below(row0, N);
+    double pf[CH] = {}, pf2[MULTI ? CH : 1] = {};     // rows past N are never loaded: zero, and never consumed
+    // one streaming pass over columns [cb0, T), RowTile::read with a start column and, for `two`, a second tile: the
+    // row delayed by b columns. body(cb, n): the lane's row is tile[lane][0 .. n), columns cb .. cb + n
     auto stream = [&](int64_t cb0, bool two, int64_t b, auto &&body) {
-        load_tile(cb0);
-        if (MULTI && two) load_tile2(cb0 - b);
+        Tile::load(pf, rows, ld, row0, T, cb0, lane, mask);
+        if constexpr (MULTI)
+            if (two) Tile::load(pf2, rows, ld, row0, T, cb0 - b, lane, mask);
         for (int64_t cb = cb0; cb < Tl; cb += CH) {
             __syncthreads();                          // the last tile (or the acf flush) has been read
-#pragma unroll
-            for (int j = 0; j < CH; ++j) tile[j * RPL + tr][tu] = pf[j];
-            if (MULTI && two) {
-#pragma unroll
-                for (int j = 0; j < CH; ++j) tile2[j * RPL + tr][tu] = pf2[j];
-            }
+            Tile::store(tile, pf, lane);
+            if constexpr (MULTI)
+                if (two) Tile::store(tile2, pf2, lane);
             __syncthreads();
             if (cb + CH < Tl) {
-                load_tile(cb + CH);
-                if (MULTI && two) load_tile2(cb + CH - b);
+                Tile::load(pf, rows, ld, row0, T, cb + CH, lane, mask);
+                if constexpr (MULTI)
+                    if (two) Tile::load(pf2, rows, ld, row0, T, cb + CH - b, lane, mask);
             }
             body(cb, (int)(cb + CH < Tl ? CH : Tl - cb));
         }
@@ -244,7 +215,7 @@ __global__ __launch_bounds__(kDgWave) __attribute__((amdgpu_waves_per_eu(MULTI ?
             const int c = lane % FW, rr = lane / FW;
             if (c < nl) {
                 double *dst = acf_out + (row0 + rr) * L + b + c;
-                asm volatile("" : "+v"(dst));         // as in load_into
+                asm volatile("" : "+v"(dst));         // as in RowTile::load
 #pragma unroll
                 for (int j = 0; j < FW; ++j)
                     if (rr < nrows - j * FR) dst[(int64_t)j * FR * L] = tile[j * FR + rr][c];

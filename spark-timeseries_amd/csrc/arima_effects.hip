@@ -12,11 +12,7 @@
 // Same operations in the same order as oracle/arima_oracle.c (orc_remove_time_dependent_effects,
 // orc_add_time_dependent_effects), so the result is bit-identical.
 //
-// Memory path: k_forecast's (arima_kernels.hip). One wave per workgroup, 64 series; the wave reads its rows as
-// [64 x kFxCh] tiles with coalesced loads (the next tile prefetched into registers while this one is consumed) and
-// transposes them through LDS. Output t is final at step t, so each lane overwrites its input in the LDS tile and the
-// whole tile leaves as coalesced row segments at kFxCh boundaries (two full 128-B lines per row when the output rows
-// are 128-B aligned). A wave reads a tile before it writes it and owns its rows, so the output may be the input.
+// Memory path: row_tile.hpp (RowTile<32>::map). Output t is final at step t; the output may be the input.
 // Templated on max(p, q) and the direction only (12 instances): p, q and d are wave-uniform run-time values over fully
 // unrolled predicated loops, so the register arrays are indexed by constants (no scratch).
 #include <hip/hip_runtime.h>
@@ -24,26 +20,25 @@
 
 #include "../../include/sparkts_arima.h"
 #include "arima_launch.hpp"
+#include "row_tile.hpp"
 
 namespace sts {
 
 constexpr int kFxMaxOrder = 5;   // p, q <= 5
 constexpr int kFxMaxD = 8;
-constexpr int kFxWave = 64;
-constexpr int kFxCh = 32;                         // time steps per tile
-constexpr int kFxRowsPerLd = kFxWave / kFxCh;     // rows per coalesced load instruction
-static_assert(kFxWave % kFxCh == 0, "tile width must divide the wave");
+using FxTile = RowTile<32>;
 static_assert(kFxMaxOrder == kFastMaxOrder, "the dispatch in the runtime sends p, q <= kFastMaxOrder here");
 
 // in_all and out_all may be the same rows (no __restrict__)
 template <int MM, bool ADD>
-__global__ __launch_bounds__(kFxWave) void k_effects(const double *in_all, int64_t ld_in,
-                                                     const double *__restrict__ coef_all, int k, double *out_all,
-                                                     int64_t ld_out, int64_t N, int T, int p, int d, int q, int I) {
+__global__ __launch_bounds__(FxTile::kWave) void k_effects(const double *in_all, int64_t ld_in,
+                                                           const double *__restrict__ coef_all, int k, double *out_all,
+                                                           int64_t ld_out, int64_t N, int T, int p, int d, int q,
+                                                           int I) {
     constexpr int kM = MM > 0 ? MM : 1;
-    __shared__ double tile[kFxWave][kFxCh + 1];
+    __shared__ FxTile::Lds tile;
     const int lane = (int)threadIdx.x;
-    const int64_t row0 = (int64_t)blockIdx.x * kFxWave;
+    const int64_t row0 = (int64_t)blockIdx.x * FxTile::kWave;
     const int64_t sid = row0 + lane;
     const bool live = sid < N;
     // coefficients [c?, phi_1..phi_p, theta_1..theta_q] (ARIMA.scala:74-77); k == 0 reads nothing
@@ -64,26 +59,9 @@ __global__ __launch_bounds__(kFxWave) void k_effects(const double *in_all, int64
 #pragma unroll
     for (int r = 0; r < kFxMaxD; ++r) lv[r] = 0.0;
 
-    // tile loads: lane reads element tu of row j * kFxRowsPerLd + tr; clamped addresses, so the loads are
-    // unconditional (values outside [0, N) x [0, T) are never consumed)
-    const int tu = lane % kFxCh, tr = lane / kFxCh;
-    double pf[kFxCh];
-    auto load_tile = [&](int cb) {
-        const int t = cb + tu < T ? cb + tu : T - 1;
-#pragma unroll
-        for (int j = 0; j < kFxCh; ++j) {
-            const int64_t gi = row0 + j * kFxRowsPerLd + tr;
-            pf[j] = in_all[(gi < N ? gi : N - 1) * ld_in + t];
-        }
-    };
-    if (T > 0) load_tile(0);
-    for (int cb = 0; cb < T; cb += kFxCh) {
-        __syncthreads();                                               // last tile's flush has read the LDS
-#pragma unroll
-        for (int j = 0; j < kFxCh; ++j) tile[j * kFxRowsPerLd + tr][tu] = pf[j];
-        __syncthreads();
-        if (cb + kFxCh < T) load_tile(cb + kFxCh);
-        const int ce = cb + kFxCh < T ? cb + kFxCh : T;
+    const unsigned long long mask = FxTile::rows_below(row0, N);
+    FxTile::map(tile, in_all, ld_in, out_all, ld_out, row0, N, T, lane, mask, [&](int cb, int n) {
+        const int ce = cb + n;
 #pragma unroll 1
         for (int t = cb; t < ce; ++t) {
             const double v = tile[lane][t - cb];
@@ -132,22 +110,13 @@ __global__ __launch_bounds__(kFxWave) void k_effects(const double *in_all, int64
             }
             tile[lane][t - cb] = w;
         }
-        __syncthreads();                                               // tile entries of every lane written
-        const int idx = cb + tu;
-        if (idx < T) {
-#pragma unroll
-            for (int j = 0; j < kFxCh; ++j) {
-                const int r = j * kFxRowsPerLd + tr;
-                if (row0 + r < N) out_all[(row0 + r) * ld_out + idx] = tile[r][tu];
-            }
-        }
-    }
+    });
 }
 
 template <bool ADD>
 static int launch_effects_dir(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out,
                               int64_t N, int T, int p, int d, int q, int I, hipStream_t s) {
-    const dim3 grid((unsigned)((N + kFxWave - 1) / kFxWave)), block(kFxWave);
+    const dim3 grid((unsigned)((N + FxTile::kWave - 1) / FxTile::kWave)), block(FxTile::kWave);
     switch (p > q ? p : q) {
 #define STS_FX_CASE(MM)                                                                                             \
     case MM:                                                                                                        \

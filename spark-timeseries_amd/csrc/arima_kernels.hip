@@ -2,6 +2,7 @@
 // The order-specialised kernels live in arima_kernels_impl.hpp and are instantiated one AR order p per
 // translation unit (arima_inst_p0..5.hip) so the build compiles in parallel.
 #include "arima_kernels_impl.hpp"
+#include "row_tile.hpp"
 
 namespace sts {
 
@@ -88,14 +89,11 @@ __global__ __launch_bounds__(256) void k_inverse_difference(const double *__rest
 // result is bit-identical. The final inverseDifferencesOfOrderD over [T-d, T+nFuture) runs in place on the
 // lane's own output row.
 //
-// Memory path (round 2): one wave per workgroup, 64 series. The wave reads its 64 rows as a [64 x kFcCh]
-// tile with coalesced loads (kFcCh consecutive doubles of 64/kFcCh rows per instruction, the next tile
-// prefetched into registers while this one is consumed) and transposes it through LDS, so each lane steps
-// through its own series from LDS. Outputs [0, T-d) go the other way: every lane writes the same output
-// index at the same step (T and d are uniform), into the same LDS ring (the consumed input's column); after each tile the
-// indices no later step can touch (< tile end - d: index x is written at step x or x + d) leave as coalesced
-// row segments. [T-d, T + nFuture) (the diffMatrix diagonal, the forecasts and their re-integration, ≤ 3 % of
-// the bytes) is written by the lane itself, as before.
+// Memory path (round 2): the input arrives through row_tile.hpp's tile loads and is transposed through LDS. Outputs
+// [0, T-d) go the other way: every lane writes the same output index at the same step (T and d are uniform), into the
+// same LDS ring (the consumed input's column); after each tile the indices no later step can touch (< tile end - d:
+// index x is written at step x or x + d) leave as coalesced row segments. [T-d, T + nFuture) (the diffMatrix
+// diagonal, the forecasts and their re-integration, ≤ 3 % of the bytes) is written by the lane itself, as before.
 // Tiles are phase-shifted by d (round 3): tile k covers steps [d + (k-1) kFcCh, d + k kFcCh), so after it exactly the
 // outputs below k kFcCh are final and every flush is a whole kFcCh-element segment at a kFcCh boundary -- with a
 // 128-B aligned output row stride (ld_out % 16 == 0) each one is two full 128-B lines per row instead of a segment
@@ -103,12 +101,11 @@ __global__ __launch_bounds__(256) void k_inverse_difference(const double *__rest
 // =======================================================================================================
 constexpr int kFcMaxOrder = 5;   // p, q <= 5 (check_orders)
 constexpr int kFcMaxD = 8;
-constexpr int kFcWave = 64;
 constexpr int kFcCh = 32;                                            // time steps per tile
+using FcTile = RowTile<kFcCh>;
+constexpr int kFcWave = FcTile::kWave;
 constexpr int kFcRing = kFcCh + kFcMaxD;                             // LDS ring columns (>= kFcCh + kFcMaxD)
-constexpr int kFcRowsPerLd = kFcWave / kFcCh;                        // rows per coalesced load instruction
 static_assert(kFcRing >= kFcCh + kFcMaxD, "output ring too small");
-static_assert(kFcWave % kFcCh == 0, "tile width must divide the wave");
 
 template <int DD, int MM>
 __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__ ts_all, int64_t ld_in,
@@ -155,30 +152,22 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
         if (idx < lim) ring[lane][idx % kFcRing] = val;   // idx is wave-uniform
         else if (live) out[idx] = val;
     };
-    // tile loads: lane reads element tu of row j * kFcRowsPerLd + tr; clamped addresses, so the loads are
-    // unconditional (values outside [0, N) x [0, T) are never consumed)
-    const int tu = lane % kFcCh, tr = lane / kFcCh;
-    double pf[kFcCh];
-    auto load_tile = [&](int cb) {
-        const int tt = cb + tu < T ? cb + tu : T - 1;
-        const int t = tt < 0 ? 0 : tt;                                 // the first tile starts before t = 0
-#pragma unroll
-        for (int j = 0; j < kFcCh; ++j) {
-            const int64_t gi = row0 + j * kFcRowsPerLd + tr;
-            pf[j] = ts_all[(gi < N ? gi : N - 1) * ld_in + t];
-        }
-    };
+    // The loads are RowTile's; its store and flush are not used: output index x is final only d steps after input x,
+    // so the tile sits in the ring (nothing stored for the first tile's columns before 0) and the flush lags it by d
+    const int tu = FcTile::col(lane);
+    const unsigned long long mask = FcTile::rows_below(row0, N);
+    double pf[kFcCh] = {};                                             // rows past N are never loaded, nor consumed
     int flushed = 0;                                                   // [0, flushed) is in HBM
     const int cb0 = d - kFcCh;                                         // first tile: steps [0, d)
-    if (T > 0) load_tile(cb0);
+    if (T > 0) FcTile::load(pf, ts_all, ld_in, row0, T, cb0, lane, mask);
     for (int cb = cb0; cb < T; cb += kFcCh) {
         __syncthreads();                                               // last tile's reads and flush done
         if (cb + tu >= 0) {
 #pragma unroll
-            for (int j = 0; j < kFcCh; ++j) ring[j * kFcRowsPerLd + tr][(cb + tu) % kFcRing] = pf[j];
+            for (int j = 0; j < kFcCh; ++j) ring[FcTile::row(lane, j)][(cb + tu) % kFcRing] = pf[j];
         }
         __syncthreads();
-        if (cb + kFcCh < T) load_tile(cb + kFcCh);
+        if (cb + kFcCh < T) FcTile::load(pf, ts_all, ld_in, row0, T, cb + kFcCh, lane, mask);
         const int ce = cb + kFcCh < T ? cb + kFcCh : T;
 #pragma unroll 1
         for (int t = cb < 0 ? 0 : cb; t < ce; ++t) {
@@ -254,7 +243,7 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
             if (idx < fe) {
 #pragma unroll
                 for (int j = 0; j < kFcCh; ++j) {
-                    const int r = j * kFcRowsPerLd + tr;
+                    const int r = FcTile::row(lane, j);
                     if (row0 + r < N) out_all[(row0 + r) * ld_out + idx] = ring[r][idx % kFcRing];
                 }
             }

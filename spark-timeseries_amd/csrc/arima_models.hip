@@ -16,75 +16,45 @@
 //
 // k_model_fit<Model>: one wave per 64 series, wave-synchronous rounds. Every live lane has one posted point; one joint
 // pass over the wave's rows computes objective and gradient at each lane's point; each lane advances its machine;
-// finished lanes are masked; the wave leaves when all are done. Rows stream through k_effects' coalesced
-// [64 series x 32 steps] LDS tiles (arima_effects.hip), the next tile prefetched into registers while this one is
-// consumed; rows of finished lanes and rows past N are not read (their tile entries are never consumed). Everything
-// carried across tile boundaries is in registers (Model::Pass). No stragglers are moved and no row stays resident:
+// finished lanes are masked; the wave leaves when all are done. Rows stream through row_tile.hpp (RowTile<32>::read);
+// rows of finished lanes and rows past N are not read (their tile entries are never consumed). Everything carried
+// across tile boundaries is in registers (Model::Pass). No stragglers are moved and no row stays resident:
 // the counters (wave passes, live lane-passes, the largest pass count of a wave) are there to decide that from numbers.
 // ARGARCH's fit is GARCH's on the AR(1) residuals: launch_ar_fit (k_ar_fit<1, 1>, the kernel behind
 // arima_fit_batch(1, 0, 0, intercept)) leaves (c, phi) and a status per series in an N x 2 workspace, and
 // k_model_fit<ArGarch> forms each residual from the raw row inside the pass (Model::A auxiliary constants per lane), so
 // no N x T residual buffer exists. Lanes whose AR stage failed never post a point and report that stage's status.
 // k_model_eval<Model>: objective and gradient at caller-given parameters, the same pass routine as the fit's.
-// k_model_effects<Model, ADD>, k_ar_effects<ADD>, k_garch_sample<AR>: one streaming pass (md_stream), N x T in, N x T
-// out, independent strides.
+// k_model_effects<Model, ADD>, k_ar_effects<ADD>, k_garch_sample<AR>: one streaming pass (md_stream, RowTile<32>::map), N x T
+// in, N x T out, independent strides.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/sparkts_arima.h"
 #include "arima_launch.hpp"
 #include "model_pass.hpp"
+#include "row_tile.hpp"
 
 namespace sts {
 
 using namespace sts::small;
 
-constexpr int kMdWave = 64;
-constexpr int kMdCh = 32;                         // time steps per tile
-constexpr int kMdRowsPerLd = kMdWave / kMdCh;     // rows per coalesced load instruction
-static_assert(kMdWave % kMdCh == 0, "tile width must divide the wave");
+using MdTile = RowTile<32>;
+constexpr int kMdWave = MdTile::kWave;
 
-typedef double MdTile[kMdWave][kMdCh + 1];
-
-// One tile of rows into registers: lane reads element tu of row j * kMdRowsPerLd + tr for the rows in `rows_mask`
-// (bit r = row row0 + r is wanted; bits of rows >= N are never set). The column is clamped, so no load leaves the row.
-__device__ __forceinline__ void md_load_tile(double (&pf)[kMdCh], const double *__restrict__ in, int64_t ld,
-                                             int64_t row0, int T, int cb, int lane, unsigned long long rows_mask) {
-    const int tu = lane % kMdCh, tr = lane / kMdCh;
-    const int t = cb + tu < T ? cb + tu : T - 1;
-#pragma unroll
-    for (int j = 0; j < kMdCh; ++j) {
-        const int r = j * kMdRowsPerLd + tr;
-        pf[j] = ((rows_mask >> r) & 1ull) ? in[(row0 + r) * ld + t] : 0.0;
-    }
-}
-
-__device__ __forceinline__ void md_store_tile(MdTile &tile, const double (&pf)[kMdCh], int lane) {
-    const int tu = lane % kMdCh, tr = lane / kMdCh;
-#pragma unroll
-    for (int j = 0; j < kMdCh; ++j) tile[j * kMdRowsPerLd + tr][tu] = pf[j];
-}
-
-// The joint pass of one round: objective f and gradient g at each live lane's point x
+// The joint pass of one round: f and gradient g at each live lane's point x; rows outside live_mask are not read
 template <class Model>
-__device__ __forceinline__ void md_wave_pass(MdTile &tile, const double *__restrict__ rows, int64_t ld, int64_t row0,
-                                             int T, int lane, unsigned long long live_mask, bool live, const double *x,
+__device__ __forceinline__ void md_wave_pass(MdTile::Lds &tile, const double *rows, int64_t ld, int64_t row0, int T,
+                                             int lane, unsigned long long live_mask, bool live, const double *x,
                                              const double *aux, double *f, double *g) {
     typename Model::Pass ps;
     ps.begin(x, aux);
-    double pf[kMdCh];
-    md_load_tile(pf, rows, ld, row0, T, 0, lane, live_mask);
-    for (int cb = 0; cb < T; cb += kMdCh) {
-        __syncthreads();                                               // the last tile has been consumed
-        md_store_tile(tile, pf, lane);
-        __syncthreads();
-        if (cb + kMdCh < T) md_load_tile(pf, rows, ld, row0, T, cb + kMdCh, lane, live_mask);
-        const int ce = cb + kMdCh < T ? cb + kMdCh : T;
+    MdTile::read(tile, rows, ld, row0, T, lane, live_mask, [&](int cb, int n) {
         if (live) {
 #pragma unroll 1
-            for (int t = cb; t < ce; ++t) ps.step(t, tile[lane][t - cb]);
+            for (int t = cb; t < cb + n; ++t) ps.step(t, tile[lane][t - cb]);
         }
-    }
+    });
     ps.end(T, f, g);
 }
 
@@ -100,7 +70,7 @@ __global__ __launch_bounds__(kMdWave) void k_model_fit(const double *__restrict_
                                                        int32_t *__restrict__ n_eval_out,
                                                        int32_t *__restrict__ n_grad_out, unsigned long long *ctl) {
     constexpr int K = Model::K, A = Model::A, NP = Model::NP;
-    __shared__ MdTile tile;
+    __shared__ MdTile::Lds tile;
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
     const int64_t sid = row0 + lane;
@@ -166,7 +136,7 @@ __global__ __launch_bounds__(kMdWave) void k_model_eval(const double *__restrict
                                                         const double *__restrict__ params, double *__restrict__ f_out,
                                                         double *__restrict__ g_out) {
     constexpr int K = Model::K;
-    __shared__ MdTile tile;
+    __shared__ MdTile::Lds tile;
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
     const int64_t sid = row0 + lane;
@@ -185,35 +155,18 @@ __global__ __launch_bounds__(kMdWave) void k_model_eval(const double *__restrict
     }
 }
 
-// One streaming pass of a wave's rows through fx.step, tile by tile: in_all and out_all are distinct ranges (the entry
-// points refuse any overlap). Nothing is read or written past column T of a row or past row N.
+// One streaming pass of a wave's rows through fx.step (the entry points refuse any overlap of in_all and out_all)
 template <class Fx>
-__device__ __forceinline__ void md_stream(MdTile &tile, Fx &fx, const double *__restrict__ in_all, int64_t ld_in,
-                                          double *__restrict__ out_all, int64_t ld_out, int64_t row0, int64_t N, int T,
-                                          int lane, bool live, unsigned long long live_mask) {
-    const int tu = lane % kMdCh, tr = lane / kMdCh;
-    double pf[kMdCh];
-    md_load_tile(pf, in_all, ld_in, row0, T, 0, lane, live_mask);
-    for (int cb = 0; cb < T; cb += kMdCh) {
-        __syncthreads();                                               // last tile's flush has read the LDS
-        md_store_tile(tile, pf, lane);
-        __syncthreads();
-        if (cb + kMdCh < T) md_load_tile(pf, in_all, ld_in, row0, T, cb + kMdCh, lane, live_mask);
-        const int ce = cb + kMdCh < T ? cb + kMdCh : T;
+__device__ __forceinline__ void md_stream(MdTile::Lds &tile, Fx &fx, const double *in_all, int64_t ld_in,
+                                          double *out_all, int64_t ld_out, int64_t row0, int64_t N, int T, int lane,
+                                          bool live) {
+    const unsigned long long mask = MdTile::rows_below(row0, N);
+    MdTile::map(tile, in_all, ld_in, out_all, ld_out, row0, N, T, lane, mask, [&](int cb, int n) {
         if (live) {
 #pragma unroll 1
-            for (int t = cb; t < ce; ++t) tile[lane][t - cb] = fx.step(t, tile[lane][t - cb]);
+            for (int t = cb; t < cb + n; ++t) tile[lane][t - cb] = fx.step(t, tile[lane][t - cb]);
         }
-        __syncthreads();                                               // tile entries of every lane written
-        const int idx = cb + tu;
-        if (idx < T) {
-#pragma unroll
-            for (int j = 0; j < kMdCh; ++j) {
-                const int r = j * kMdRowsPerLd + tr;
-                if (row0 + r < N) out_all[(row0 + r) * ld_out + idx] = tile[r][tu];
-            }
-        }
-    }
+    });
 }
 
 // params: N x Model::NP (the pass's constants, then the optimizer's parameters)
@@ -223,7 +176,7 @@ __global__ __launch_bounds__(kMdWave) void k_model_effects(const double *__restr
                                                            double *__restrict__ out_all, int64_t ld_out, int64_t N,
                                                            int T) {
     constexpr int NP = Model::NP;
-    __shared__ MdTile tile;
+    __shared__ MdTile::Lds tile;
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
     const int64_t sid = row0 + lane;
@@ -233,7 +186,7 @@ __global__ __launch_bounds__(kMdWave) void k_model_effects(const double *__restr
     for (int j = 0; j < NP; ++j) x[j] = live ? params[sid * NP + j] : 0.0;
     typename Model::template Fx<ADD> fx;
     fx.begin(x);
-    md_stream(tile, fx, in_all, ld_in, out_all, ld_out, row0, N, T, lane, live, __ballot(live));
+    md_stream(tile, fx, in_all, ld_in, out_all, ld_out, row0, N, T, lane, live);
 }
 
 // GARCHModel.sample (AR == false, params N x 3) / ARGARCHModel.sample (AR == true, params N x 5): z in, series out
@@ -243,7 +196,7 @@ __global__ __launch_bounds__(kMdWave) void k_garch_sample(const double *__restri
                                                           double *__restrict__ out_all, int64_t ld_out, int64_t N,
                                                           int T) {
     constexpr int NP = GarchSample<AR>::NP;
-    __shared__ MdTile tile;
+    __shared__ MdTile::Lds tile;
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
     const int64_t sid = row0 + lane;
@@ -253,7 +206,7 @@ __global__ __launch_bounds__(kMdWave) void k_garch_sample(const double *__restri
     for (int j = 0; j < NP; ++j) x[j] = live ? params[sid * NP + j] : 0.0;
     GarchSample<AR> fx;
     fx.begin(x);
-    md_stream(tile, fx, z_all, ld_in, out_all, ld_out, row0, N, T, lane, live, __ballot(live));
+    md_stream(tile, fx, z_all, ld_in, out_all, ld_out, row0, N, T, lane, live);
 }
 
 // ARModel's pair at a runtime order 1 <= p <= kArMaxP; coef N x (1 + p) = (c, phi_1 .. phi_p). Each lane's
@@ -266,7 +219,7 @@ __global__ __launch_bounds__(kMdWave) void k_ar_effects(const double *__restrict
                                                         const double *__restrict__ coef_all, int p,
                                                         double *__restrict__ out_all, int64_t ld_out, int64_t N,
                                                         int T) {
-    __shared__ MdTile tile;
+    __shared__ MdTile::Lds tile;
     __shared__ double cf[kMdWave][kArLdsStride], hist[kMdWave][kArLdsStride];
     const int lane = (int)threadIdx.x;
     const int64_t row0 = (int64_t)blockIdx.x * kMdWave;
@@ -275,7 +228,7 @@ __global__ __launch_bounds__(kMdWave) void k_ar_effects(const double *__restrict
     for (int j = 0; j <= p; ++j) cf[lane][j] = live ? coef_all[sid * (1 + p) + j] : 0.0;
     ArFx<ADD> fx;
     fx.begin(cf[lane], p, hist[lane]);
-    md_stream(tile, fx, in_all, ld_in, out_all, ld_out, row0, N, T, lane, live, __ballot(live));
+    md_stream(tile, fx, in_all, ld_in, out_all, ld_out, row0, N, T, lane, live);
 }
 
 static inline dim3 md_grid(int64_t N) { return dim3((unsigned)((N + kMdWave - 1) / kMdWave)); }
