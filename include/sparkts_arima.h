@@ -154,7 +154,9 @@ int         arima_synchronize(arima_handle *h);
  * that copy arima_fit_batch's rows into pinned blocks for the upload; default 0 = upload from pageable memory through
  * the HIP runtime's staging), "chain_overhead" (k_cg_fit's objective-pass width model; 0 = the kernel's),
  * "diag_slice_bytes" (residual workspace of one slice of arima_residual_diagnostics_batch*; 0, the default, = 60 % of
- * the free HBM, at least 1 GiB; results never depend on it). */
+ * the free HBM, at least 1 GiB; results never depend on it), "regress_slice_bytes" (design workspace of one slice of
+ * the arima_arx_*, arima_bgtest_* and arima_bptest_* calls; 0, the default, = the same rule; results never depend on
+ * it). */
 int         arima_set_option(arima_handle *h, const char *name, int64_t value);
 /* Current value of a tuning knob (the names arima_set_option takes); ARIMA_E_INVALID_ARG for an unknown name. */
 int         arima_get_option(const arima_handle *h, const char *name, int64_t *value);
@@ -261,6 +263,65 @@ int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_ser
                                             const double *d_coef, int32_t max_lag, double *d_acf_out,
                                             double *d_dw_out, double *d_lb_stat_out, double *d_lb_pvalue_out,
                                             void *stream);
+/* ---- regressions over a regressor matrix: AutoregressionX, bgtest, bptest over a batch --------------------------- *
+ * One computation, commons-math3 OLSMultipleLinearRegression (QR at threshold 0) over a design that is not made only
+ * of a series' own lags, in the reference's arithmetic and order: coefficients, predictions and the test statistics
+ * are bit-identical to tests/regress_ref.py; the p-values restate commons' chi-squared tail (csrc/arima_chisq.hpp)
+ * and agree with it to a tolerance.
+ * xreg / factors: per series n_xcols rows of T values, the column-major DenseMatrix(T, k) of the reference.
+ * x_series_stride (elements): 0 = one matrix shared by every series, else the distance between two series' matrices,
+ * at least n_xcols * T. n_xcols == 0 is legal for the arx entry points (xreg may then be NULL).
+ * AutoregressionX.fitModel(y, x, yMaxLag, xMaxLag, includeOriginalX, noIntercept) (AutoregressionX.scala:48-92): with
+ * maxLag = max(yMaxLag, xMaxLag) there are R = T - maxLag rows; row r is time t = r + maxLag with the predictors
+ * y(t-1) .. y(t-yMaxLag), then for every x column in order x_c(t-1) .. x_c(t-xMaxLag), then, with includeOriginalX,
+ * x_0(t) .. x_{k-1}(t); K = arima_arx_num_coef of them. coef_out N x (1 + K) = (c, coefficients), c = 0.0 under
+ * no_intercept. status_out N carries what the reference throws, per series: ARIMA_ST_SERIES_TOO_SHORT (R < 0),
+ * ARIMA_ST_NO_DATA (R == 0, or no column at all), ARIMA_ST_NOT_ENOUGH_DATA (K + 1 > R), ARIMA_ST_SINGULAR (an rDiag
+ * of the QR exactly 0); a failed series has NaN outputs and never aborts the batch. NaN and Inf propagate as in the
+ * JVM (status OK).
+ * ARXModel.predict (:117-130): out N x (T - maxLag), results(r) = c then += value * coefficients(col) in column
+ * order; coef N x (1 + K) as arima_arx_fit_batch writes it. T < maxLag returns ARIMA_E_INVALID_ARG.
+ * bgtest(residuals, factors, maxLag) (TimeSeriesStatisticalTests.scala:276-288): rows t = maxLag .. T-1 of
+ * [factors(t, .), u(t-1) .. u(t-maxLag)] against u(t), with an intercept; stat = (T - maxLag) * R^2, p-value its
+ * chi-squared(maxLag) upper tail. max_lag < 1 returns ARIMA_E_INVALID_ARG (ChiSquaredDistribution(0) throws).
+ * bptest(residuals, factors) (:320-329): T rows of factors(t, .) against u(t) * u(t), with an intercept;
+ * stat = T * R^2, df = n_xcols. n_xcols < 1 returns ARIMA_E_INVALID_ARG. R^2 is calculateRSquared of commons-math3
+ * 3.4.1: 1 - RSS / TSS, TSS by SecondMoment's running update (an unpinned reading). A failed series
+ * has NaN statistic and p-value and its status as above.
+ * Negative lags or column counts, T < 0 and an x_series_stride in (0, n_xcols * T) return ARIMA_E_INVALID_ARG; more
+ * than 64 design columns (the ones column included) return ARIMA_E_UNSUPPORTED; N == 0 returns ARIMA_OK and writes
+ * nothing. Every output is required; outputs that overlap an input or one another return ARIMA_E_INVALID_ARG. The
+ * design of a slice of series lives in a workspace owned by the handle ("regress_slice_bytes"; 0, the default, = the
+ * rule of "diag_slice_bytes"; slices are whole blocks of 64 series and results never depend on their size).        */
+int arima_arx_num_coef(int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag, int32_t include_original_x);
+int arima_arx_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *xreg,
+                        int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
+                        int32_t include_original_x, int32_t no_intercept, double *coef_out, int32_t *status_out);
+int arima_arx_predict_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *xreg,
+                            int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
+                            int32_t include_original_x, const double *coef, double *out);
+int arima_bgtest_batch(arima_handle *h, const double *residuals, int64_t n_series, int32_t T, const double *factors,
+                       int64_t x_series_stride, int32_t n_xcols, int32_t max_lag, double *stat_out,
+                       double *pvalue_out, int32_t *status_out);
+int arima_bptest_batch(arima_handle *h, const double *residuals, int64_t n_series, int32_t T, const double *factors,
+                       int64_t x_series_stride, int32_t n_xcols, double *stat_out, double *pvalue_out,
+                       int32_t *status_out);
+/* Same, device-resident: d_series / d_residuals N x T (row stride ld >= T, else ARIMA_E_INVALID_ARG), device
+ * regressors and outputs; d_out of the prediction N x (T - maxLag) with row stride ld_out >= T - maxLag            */
+int arima_arx_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                               const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
+                               int32_t x_max_lag, int32_t include_original_x, int32_t no_intercept,
+                               double *d_coef_out, int32_t *d_status_out, void *stream);
+int arima_arx_predict_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                   const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
+                                   int32_t x_max_lag, int32_t include_original_x, const double *d_coef, double *d_out,
+                                   int64_t ld_out, void *stream);
+int arima_bgtest_batch_device(arima_handle *h, const double *d_residuals, int64_t n_series, int32_t T, int64_t ld,
+                              const double *d_factors, int64_t x_series_stride, int32_t n_xcols, int32_t max_lag,
+                              double *d_stat_out, double *d_pvalue_out, int32_t *d_status_out, void *stream);
+int arima_bptest_batch_device(arima_handle *h, const double *d_residuals, int64_t n_series, int32_t T, int64_t ld,
+                              const double *d_factors, int64_t x_series_stride, int32_t n_xcols, double *d_stat_out,
+                              double *d_pvalue_out, int32_t *d_status_out, void *stream);
 /* ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815) for N coefficient rows, flags_out N */
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t n_series, int32_t p, int32_t q,
                             int32_t include_intercept, uint8_t *flags_out);

@@ -58,6 +58,77 @@ int launch_ar_effects(const double *in, int64_t ld_in, const double *coef, int p
 // GARCHModel.sample (kModelGarch) / ARGARCHModel.sample (kModelArGarch) from the caller's standard normals z
 int launch_garch_sample(int model, const double *z, int64_t ld_in, const double *params, double *out, int64_t ld_out,
                         int64_t N, int T, hipStream_t s);
+// ---- regressions over a design matrix (arima_regress.hip): AutoregressionX, bgtest, bptest ----
+// commons' OLSMultipleLinearRegression over a design that is not made only of a series' own lags. A design has R rows
+// and C columns (the ones column included); every column is a window of one source row: value(r) = source[off + r].
+constexpr int kRgMaxCols = 64;     // C of k_regress_qr
+constexpr int kRgArx = 0, kRgBg = 1, kRgBp = 2;
+// RgCol::src: literal 1.0, the per-series row; j >= 0: regressor column j
+constexpr int kRgOnes = -2, kRgSelf = -1;
+struct RgCol {
+    int src, off;
+    bool sq;                                       // the value squared (bptest's response)
+};
+// kind kRgArx: AutoregressionX.fitModel(y, x, lag_a = yMaxLag, lag_b = xMaxLag, orig = includeOriginalX, icpt =
+// !noIntercept); kRgBg: bgtest(residuals, factors, lag_a = maxLag); kRgBp: bptest(residuals, factors). T values per
+// row, k regressor columns
+struct RgDesign {
+    int kind, T, k, lag_a, lag_b, orig, icpt;
+    __host__ __device__ int max_lag() const {
+        return kind == kRgBp ? 0 : kind == kRgBg ? lag_a : (lag_a > lag_b ? lag_a : lag_b);
+    }
+    __host__ __device__ int rows() const { return T - max_lag(); }
+    // predictors without the ones column (int64: the entry points check it before anything narrows)
+    __host__ __device__ int64_t num_pred() const {
+        if (kind == kRgArx) return (int64_t)lag_a + (int64_t)k * lag_b + (orig ? k : 0);
+        return (int64_t)k + (kind == kRgBg ? lag_a : 0);
+    }
+    __host__ __device__ int cols() const { return (int)num_pred() + (icpt ? 1 : 0); }
+    // column c of the design in the reference's order; c == cols() is the response
+    __host__ __device__ RgCol col(int c) const {
+        const int m = max_lag();
+        if (c == cols()) return {kRgSelf, m, kind == kRgBp};
+        if (icpt && c == 0) return {kRgOnes, 0, false};
+        c -= icpt ? 1 : 0;
+        if (kind == kRgArx) {                      // y(t-1) .. y(t-a), per column x_c(t-1) .. x_c(t-b), then x_0(t) ..
+            if (c < lag_a) return {kRgSelf, m - (c + 1), false};
+            c -= lag_a;
+            if (c < k * lag_b) return {c / lag_b, m - (c % lag_b + 1), false};
+            return {c - k * lag_b, m, false};
+        }
+        if (c < k) return {c, m, false};           // factors(t, .), then bgtest's u(t-1) .. u(t-maxLag)
+        return {kRgSelf, m - (c - k + 1), false};
+    }
+};
+// y: the per-series rows (series or residuals), N x T with row stride ld; x: per series k rows of T values (the
+// column-major DenseMatrix(T, k)), series stride xs elements, 0 = one matrix shared by every series
+struct RgSrc {
+    const double *y;
+    int64_t ld;
+    const double *x;
+    int64_t xs;
+    RgSrc at(int64_t f) const { return {y + f * ld, ld, x ? x + f * xs : nullptr, xs}; }
+};
+// doubles of the workspace of n series: whole blocks of 64 series, element (series 64 b + lane, column c, row r) at
+// ws[((b (C + 1) + c) R + r) 64 + lane], column C the response
+inline int64_t rg_ws_doubles(int64_t n, int R, int C) { return (n + 63) / 64 * (int64_t)(C + 1) * R * 64; }
+// the launchers below need rows() >= 1 and 1 <= cols() <= kRgMaxCols (the entry points report every other shape)
+int launch_regress_assemble(const RgDesign &d, const RgSrc &src, int64_t N, double *ws, hipStream_t s);
+// commons' QR in place on the assembled workspace, then Solver.solve on the response column: beta (C values) to
+// beta_out[i * ldb + boff ..] and, with c_zero, 0.0 to beta_out[i * ldb]; a singular series: status SINGULAR, NaNs
+int launch_regress_qr(double *ws, int64_t N, int R, int C, double *beta_out, int ldb, int boff, int c_zero,
+                      int32_t *status_out, hipStream_t s);
+// calculateRSquared on a freshly assembled workspace: stat = nobs * R^2 and its chi-squared(df) upper tail; NaNs where
+// status is not OK. beta N x C
+int launch_regress_r2(const double *ws, const double *beta, const int32_t *status, int64_t N, int R, int C, int nobs,
+                      int df, double *stat_out, double *pvalue_out, hipStream_t s);
+// ARXModel.predict straight from the sources: coef N x (1 + K) = (c, coefficients), out N x rows() (row stride ld_out)
+int launch_arx_predict(const RgDesign &d, const RgSrc &src, const double *coef, double *out, int64_t ld_out, int64_t N,
+                       hipStream_t s);
+// a shape the reference refuses for every series alike: status to status_out, NaN to the n0 / n1 doubles per series
+// of out0 / out1 (null: none)
+int launch_regress_refuse(int64_t N, int32_t status, int32_t *status_out, double *out0, int n0, double *out1, int n1,
+                          hipStream_t s);
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.

@@ -277,6 +277,9 @@ struct arima_handle {
     // residual diagnostics (arima_residual_diagnostics_batch*): one slice of residuals
     int64_t diag_slice_bytes = 0;  // option "diag_slice_bytes"; 0 = 60 % of the free HBM, at least 1 GiB
     DevBuf dg_resid;
+    // the design-matrix regressions (arima_arx_*, arima_bgtest_*, arima_bptest_*): one slice's designs, the tests' beta
+    int64_t regress_slice_bytes = 0;   // option "regress_slice_bytes"; 0 = the rule of diag_slice_bytes
+    DevBuf rg_ws, rg_beta;
     // the small models (EWMA, GARCH): the fit kernel's counters of the last fit
     DevBuf md_ctl;
     int64_t md_last_n = -1;        // series of the last EWMA / GARCH / ARGARCH fit (-1: none yet)
@@ -738,6 +741,7 @@ int arima_set_option(arima_handle *h, const char *name, int64_t value) {
     }
     if (!strcmp(name, "fit_slice_bytes")) { h->fit_slice_bytes = std::max<int64_t>(0, value); return ARIMA_OK; }
     if (!strcmp(name, "diag_slice_bytes")) { h->diag_slice_bytes = std::max<int64_t>(0, value); return ARIMA_OK; }
+    if (!strcmp(name, "regress_slice_bytes")) { h->regress_slice_bytes = std::max<int64_t>(0, value); return ARIMA_OK; }
     return set_err(h, ARIMA_E_INVALID_ARG, "unknown option");
 }
 
@@ -753,7 +757,7 @@ int arima_get_option(const arima_handle *hc, const char *name, int64_t *value) {
         {"search_express_blocks", h->search_express_blocks}, {"donate_evals", h->donate_evals},
         {"donate_evals_drained", h->donate_evals_drained}, {"fuse_diff", h->fuse_mode}, {"autofit_slice", h->autofit_slice},
         {"host_copy_threads", h->host_copy_threads}, {"chain_overhead", h->chain_overhead}, {"host_tail", h->host_tail},
-        {"diag_slice_bytes", h->diag_slice_bytes}};
+        {"diag_slice_bytes", h->diag_slice_bytes}, {"regress_slice_bytes", h->regress_slice_bytes}};
     for (const auto &o : opts)
         if (!strcmp(name, o.n)) {
             *value = o.v;
@@ -1634,6 +1638,245 @@ int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_ser
     PASSCHK(f.begin(stream));
     RCCHK(h, residual_diag_dev(h, d_series, N, T, ld, p, d, q, I, d_coef, max_lag, o, f.s()), "residual diagnostics");
     return f.finish();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// regressions over a design matrix (arima_regress.hip): AutoregressionX.fitModel, ARXModel.predict, bgtest, bptest
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+using sts::RgDesign;
+using sts::RgSrc;
+
+// What commons' validateSampleData and newXSampleData (and, before them, the reference's slicing) throw for a shape,
+// the same for every series of the call, in orc_ols's order
+int32_t regress_shape_status(const RgDesign &d) {
+    const int R = d.rows();
+    if (R < 0) return ARIMA_ST_SERIES_TOO_SHORT;
+    if (R == 0) return ARIMA_ST_NO_DATA;
+    if (d.num_pred() + 1 > R) return ARIMA_ST_NOT_ENOUGH_DATA;
+    if (d.cols() == 0) return ARIMA_ST_NO_DATA;
+    return ARIMA_ST_OK;
+}
+
+// argument rules shared by the eight entry points; *done: nothing to compute (ARIMA_OK)
+int regress_check(arima_handle *h, const RgDesign &d, int64_t N, int64_t ld, int64_t xs, bool *done) {
+    *done = false;
+    if (N < 0 || d.T < 0 || ld < d.T || d.k < 0 || d.lag_a < 0 || d.lag_b < 0)
+        return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    // ChiSquaredDistribution(0) throws
+    if (d.kind == sts::kRgBg && d.lag_a < 1) return set_err(h, ARIMA_E_INVALID_ARG, "max_lag < 1");
+    if (d.kind == sts::kRgBp && d.k < 1) return set_err(h, ARIMA_E_INVALID_ARG, "n_xcols < 1");
+    if (xs != 0 && xs < (int64_t)d.k * d.T) return set_err(h, ARIMA_E_INVALID_ARG, "x_series_stride below n_xcols * T");
+    if (d.num_pred() + (d.icpt ? 1 : 0) > sts::kRgMaxCols) return set_err(h, ARIMA_E_UNSUPPORTED, "at most 64 columns");
+    *done = N == 0;
+    return ARIMA_OK;
+}
+
+// doubles of the caller's regressor block: one matrix, or N of them x_series_stride apart
+int64_t regress_x_doubles(const RgDesign &d, int64_t N, int64_t xs) {
+    const int64_t one = (int64_t)d.k * d.T;
+    return one == 0 ? 0 : (xs == 0 ? one : (N - 1) * xs + one);
+}
+
+bool regress_null_input(const RgDesign &d, const RgSrc &src) { return d.T > 0 && (!src.y || (d.k > 0 && !src.x)); }
+
+// The fit (coef_out: N x (1 + K)) or the test (stat_out, pvalue_out: N) of every series, slice by slice: assemble, QR
+// and, for a test, assemble again and calculateRSquared
+int regress_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N, double *coef_out, double *stat_out,
+                double *pvalue_out, int32_t *status_out, hipStream_t s) {
+    const bool test = d.kind != sts::kRgArx;
+    const int K = (int)d.num_pred(), C = d.cols(), R = d.rows();
+    const int32_t shape = regress_shape_status(d);
+    if (shape != ARIMA_ST_OK) {
+        RCCHK(h, sts::launch_regress_refuse(N, shape, status_out, test ? stat_out : coef_out, test ? 1 : 1 + K,
+                                            test ? pvalue_out : nullptr, 1, s), "regression");
+        return ARIMA_OK;
+    }
+    int64_t slice_bytes = h->regress_slice_bytes;
+    if (slice_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
+    }
+    const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, (int64_t)(C + 1) * R);
+    RCCHK(h, h->rg_ws.ensure((size_t)sts::rg_ws_doubles(std::min(slice, N), R, C) * sizeof(double)),
+          "regression workspace");
+    if (test) RCCHK(h, h->rg_beta.ensure((size_t)std::min(slice, N) * C * sizeof(double)), "regression workspace");
+    double *ws = h->rg_ws.as<double>(), *beta = h->rg_beta.as<double>();
+    for (int64_t f = 0; f < N; f += slice) {
+        const int64_t n = std::min(slice, N - f);
+        RCCHK(h, sts::launch_regress_assemble(d, src.at(f), n, ws, s), "design");
+        if (!test) {
+            RCCHK(h, sts::launch_regress_qr(ws, n, R, C, coef_out + f * (1 + K), 1 + K, d.icpt ? 0 : 1, d.icpt ? 0 : 1,
+                                            status_out + f, s), "qr");
+            continue;
+        }
+        RCCHK(h, sts::launch_regress_qr(ws, n, R, C, beta, C, 0, 0, status_out + f, s), "qr");
+        RCCHK(h, sts::launch_regress_assemble(d, src.at(f), n, ws, s), "design");   // the QR ran in place
+        // nObs = T - maxLag (bgtest), T (bptest): the rows; df = maxLag, k
+        RCCHK(h, sts::launch_regress_r2(ws, beta, status_out + f, n, R, C, R, d.kind == sts::kRgBg ? d.lag_a : d.k,
+                                        stat_out + f, pvalue_out + f, s), "r squared");
+    }
+    return ARIMA_OK;
+}
+
+int regress_host(arima_handle *h, const RgDesign &d, const double *rows, int64_t N, const double *xreg, int64_t xs,
+                 double *coef_out, double *stat_out, double *pvalue_out, int32_t *status_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kHostBuffers);
+    bool done;
+    PASSCHK(regress_check(h, d, N, d.T, xs, &done));
+    if (done) return ARIMA_OK;
+    const bool test = d.kind != sts::kRgArx;
+    if (regress_null_input(d, {rows, d.T, xreg, xs}) || !status_out || (test ? !stat_out || !pvalue_out : !coef_out))
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * d.T,
+                 x_bytes = (size_t)regress_x_doubles(d, N, xs) * sizeof(double),
+                 o0 = test ? nd : nd * (1 + (size_t)d.num_pred()), o1 = test ? nd : 0,
+                 st_bytes = (size_t)N * sizeof(int32_t);
+    double *out0 = test ? stat_out : coef_out;
+    PASSCHK(check_overlap(h, {ByteSpan(rows, row_bytes), ByteSpan(xreg, x_bytes)},
+                          {ByteSpan(out0, o0), ByteSpan(pvalue_out, o1), ByteSpan(status_out, st_bytes)}));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(rows, row_bytes), stage_in(xreg, x_bytes), stage_out(out0, o0),
+                     stage_optional_out(test ? pvalue_out : nullptr, o1), stage_out(status_out, st_bytes)}));
+    const RgSrc src{f.dev<double>(0), d.T, x_bytes ? f.dev<double>(1) : nullptr, xs};
+    PASSCHK(regress_dev(h, d, src, N, test ? nullptr : f.dev<double>(2), test ? f.dev<double>(2) : nullptr,
+                        f.dev<double>(3), f.dev<int32_t>(4), f.s()));
+    return f.finish();
+}
+
+int regress_device(arima_handle *h, const RgDesign &d, const double *d_rows, int64_t N, int64_t ld,
+                   const double *d_xreg, int64_t xs, double *coef_out, double *stat_out, double *pvalue_out,
+                   int32_t *status_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kDeviceBuffers);
+    bool done;
+    PASSCHK(regress_check(h, d, N, ld, xs, &done));
+    if (done) return ARIMA_OK;
+    const bool test = d.kind != sts::kRgArx;
+    const RgSrc src{d_rows, ld, (int64_t)d.k * d.T ? d_xreg : nullptr, xs};
+    if (regress_null_input(d, {d_rows, ld, d_xreg, xs}) || !status_out || (test ? !stat_out || !pvalue_out : !coef_out))
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int64_t nd = N * (int64_t)sizeof(double);
+    double *out0 = test ? stat_out : coef_out;
+    PASSCHK(check_overlap(h, {ByteSpan(d_rows, ((N - 1) * ld + d.T) * (int64_t)sizeof(double)),
+                              ByteSpan(d_xreg, regress_x_doubles(d, N, xs) * (int64_t)sizeof(double))},
+                          {ByteSpan(out0, test ? nd : nd * (1 + d.num_pred())),
+                           ByteSpan(test ? pvalue_out : nullptr, nd),
+                           ByteSpan(status_out, N * (int64_t)sizeof(int32_t))}));
+    PASSCHK(f.begin(stream));
+    PASSCHK(regress_dev(h, d, src, N, coef_out, stat_out, pvalue_out, status_out, f.s()));
+    return f.finish();
+}
+
+RgDesign arx_design(int32_t T, int32_t k, int32_t y_max_lag, int32_t x_max_lag, int32_t orig, int32_t no_intercept) {
+    return {sts::kRgArx, T, k, y_max_lag, x_max_lag, orig ? 1 : 0, no_intercept ? 0 : 1};
+}
+
+// ARXModel.predict's own rule on top of regress_check: the reference's slicing throws for T < maxLag
+int predict_check(arima_handle *h, const RgDesign &d, int64_t N, int64_t ld, int64_t xs, int64_t ld_out, bool *done) {
+    PASSCHK(regress_check(h, d, N, ld, xs, done));
+    if (d.rows() < 0 || ld_out < d.rows()) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    *done = *done || d.rows() == 0;
+    return ARIMA_OK;
+}
+}  // namespace
+
+int arima_arx_num_coef(int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag, int32_t include_original_x) {
+    if (n_xcols < 0 || y_max_lag < 0 || x_max_lag < 0) return ARIMA_E_INVALID_ARG;
+    const int64_t K = arx_design(0, n_xcols, y_max_lag, x_max_lag, include_original_x, 1).num_pred();
+    return K > INT32_MAX ? ARIMA_E_INVALID_ARG : (int)K;
+}
+
+int arima_arx_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
+                        int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
+                        int32_t include_original_x, int32_t no_intercept, double *coef_out, int32_t *status_out) {
+    return regress_host(h, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept), series, N,
+                        xreg, x_series_stride, coef_out, nullptr, nullptr, status_out);
+}
+
+int arima_arx_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                               const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
+                               int32_t x_max_lag, int32_t include_original_x, int32_t no_intercept, double *d_coef_out,
+                               int32_t *d_status_out, void *stream) {
+    return regress_device(h, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept), d_series,
+                          N, ld, d_xreg, x_series_stride, d_coef_out, nullptr, nullptr, d_status_out, stream);
+}
+
+int arima_arx_predict_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
+                            int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
+                            int32_t include_original_x, const double *coef, double *out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kHostBuffers);
+    const RgDesign d = arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, 1);
+    bool done;
+    PASSCHK(predict_check(h, d, N, T, x_series_stride, d.rows(), &done));
+    if (done) return ARIMA_OK;
+    if (regress_null_input(d, {series, T, xreg, x_series_stride}) || !coef || !out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
+                 x_bytes = (size_t)regress_x_doubles(d, N, x_series_stride) * sizeof(double),
+                 coef_bytes = nd * (1 + (size_t)d.num_pred()), out_bytes = nd * d.rows();
+    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(coef, coef_bytes)},
+                          {ByteSpan(out, out_bytes)}));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(coef, coef_bytes),
+                     stage_out(out, out_bytes)}));
+    const RgSrc src{f.dev<double>(0), T, x_bytes ? f.dev<double>(1) : nullptr, x_series_stride};
+    RCCHK(h, sts::launch_arx_predict(d, src, f.dev<double>(2), f.dev<double>(3), d.rows(), N, f.s()), "predict");
+    return f.finish();
+}
+
+int arima_arx_predict_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                   const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
+                                   int32_t x_max_lag, int32_t include_original_x, const double *d_coef, double *d_out,
+                                   int64_t ld_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kDeviceBuffers);
+    const RgDesign d = arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, 1);
+    bool done;
+    PASSCHK(predict_check(h, d, N, ld, x_series_stride, ld_out, &done));
+    if (done) return ARIMA_OK;
+    if (regress_null_input(d, {d_series, ld, d_xreg, x_series_stride}) || !d_coef || !d_out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int64_t sd = (int64_t)sizeof(double);
+    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
+                              ByteSpan(d_xreg, regress_x_doubles(d, N, x_series_stride) * sd),
+                              ByteSpan(d_coef, N * (1 + d.num_pred()) * sd)},
+                          {ByteSpan(d_out, ((N - 1) * ld_out + d.rows()) * sd)}));
+    PASSCHK(f.begin(stream));
+    const RgSrc src{d_series, ld, (int64_t)d.k * T ? d_xreg : nullptr, x_series_stride};
+    RCCHK(h, sts::launch_arx_predict(d, src, d_coef, d_out, ld_out, N, f.s()), "predict");
+    return f.finish();
+}
+
+int arima_bgtest_batch(arima_handle *h, const double *residuals, int64_t N, int32_t T, const double *factors,
+                       int64_t x_series_stride, int32_t n_xcols, int32_t max_lag, double *stat_out, double *pvalue_out,
+                       int32_t *status_out) {
+    return regress_host(h, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, residuals, N, factors, x_series_stride, nullptr,
+                        stat_out, pvalue_out, status_out);
+}
+
+int arima_bgtest_batch_device(arima_handle *h, const double *d_residuals, int64_t N, int32_t T, int64_t ld,
+                              const double *d_factors, int64_t x_series_stride, int32_t n_xcols, int32_t max_lag,
+                              double *d_stat_out, double *d_pvalue_out, int32_t *d_status_out, void *stream) {
+    return regress_device(h, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, d_residuals, N, ld, d_factors, x_series_stride,
+                          nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
+}
+
+int arima_bptest_batch(arima_handle *h, const double *residuals, int64_t N, int32_t T, const double *factors,
+                       int64_t x_series_stride, int32_t n_xcols, double *stat_out, double *pvalue_out,
+                       int32_t *status_out) {
+    return regress_host(h, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, residuals, N, factors, x_series_stride, nullptr,
+                        stat_out, pvalue_out, status_out);
+}
+
+int arima_bptest_batch_device(arima_handle *h, const double *d_residuals, int64_t N, int32_t T, int64_t ld,
+                              const double *d_factors, int64_t x_series_stride, int32_t n_xcols, double *d_stat_out,
+                              double *d_pvalue_out, int32_t *d_status_out, void *stream) {
+    return regress_device(h, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, d_residuals, N, ld, d_factors, x_series_stride,
+                          nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------

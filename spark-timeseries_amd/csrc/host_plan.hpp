@@ -1,8 +1,9 @@
 // host_plan.hpp — the host-side sizing arithmetic of arima_runtime.cpp as pure functions: the host path's chunk
 // schedule, the layout of one chunk's results in pinned staging, the layout of a host-buffer call's staged arrays, the
 // byte-span overlap rule of the entry points, the partition par_memcpy hands its threads, and the rows per slice of the
-// sliced device fit and of the residual diagnostics. No HIP headers: a CPU program includes this file and sweeps the
-// functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of the formulas.
+// sliced device fit, of the residual diagnostics and of the design-matrix regressions. No HIP headers: a CPU program
+// includes this file and sweeps the functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of
+// the formulas.
 #pragma once
 
 #include <algorithm>
@@ -139,6 +140,12 @@ inline int64_t fit_slice_rows(int64_t slice_bytes, int64_t ld_doubles) {
 // rows of one slice of the residual diagnostics: multiples of 64 rows within slice_bytes, at least 64
 inline int64_t diag_slice_rows(int64_t slice_bytes, int64_t ld_doubles) {
     return std::max<int64_t>(64, slice_bytes / (ld_doubles * (int64_t)sizeof(double)) / 64 * 64);
+}
+
+// series of one slice of the design-matrix regressions (AutoregressionX, bgtest, bptest): whole blocks of 64 series
+// whose workspaces of ws_doubles doubles per series fit slice_bytes, at least one block
+inline int64_t regress_slice_rows(int64_t slice_bytes, int64_t ws_doubles) {
+    return std::max<int64_t>(64, slice_bytes / (std::max<int64_t>(ws_doubles, 1) * (int64_t)sizeof(double)) / 64 * 64);
 }
 
 }  // namespace plan

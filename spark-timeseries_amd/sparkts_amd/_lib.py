@@ -67,6 +67,9 @@ EXPORTED = [
     "arima_argarch_add_effects_batch_device", "arima_ar_remove_effects_batch", "arima_ar_add_effects_batch",
     "arima_ar_remove_effects_batch_device", "arima_ar_add_effects_batch_device", "arima_garch_sample_batch",
     "arima_argarch_sample_batch", "arima_garch_sample_batch_device", "arima_argarch_sample_batch_device",
+    "arima_arx_num_coef", "arima_arx_fit_batch", "arima_arx_fit_batch_device", "arima_arx_predict_batch",
+    "arima_arx_predict_batch_device", "arima_bgtest_batch", "arima_bgtest_batch_device", "arima_bptest_batch",
+    "arima_bptest_batch_device",
 ]
 
 # the small models (EWMA.scala, GARCH.scala): parameters per series; ARGARCH's are (c, phi, omega, alpha, beta)
@@ -204,6 +207,17 @@ def load():
         for m in ("garch", "argarch"):
             getattr(L, f"arima_{m}_sample_batch").argtypes = [H, _dp, _i64, _i32, _dp, _dp]
             getattr(L, f"arima_{m}_sample_batch_device").argtypes = [H, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp]
+        L.arima_arx_num_coef.argtypes = [_i32, _i32, _i32, _i32]
+        L.arima_arx_fit_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _dp, _i32p]
+        L.arima_arx_fit_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp,
+                                                 _vp, _vp]
+        L.arima_arx_predict_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _i32, _i32, _dp, _dp]
+        L.arima_arx_predict_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp,
+                                                     _vp, _i64, _vp]
+        L.arima_bgtest_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _dp, _dp, _i32p]
+        L.arima_bgtest_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
+        L.arima_bptest_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _dp, _dp, _i32p]
+        L.arima_bptest_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
         _lib = L
         return L
 
@@ -644,6 +658,113 @@ class Engine:
                                                                    int(bool(include_intercept)), d_coef, max_lag,
                                                                    d_acf, d_dw, d_lb_stat, d_lb_pvalue, stream),
                     "arima_residual_diagnostics_batch_device")
+        if blocking:
+            self.synchronize()
+
+    # ---- regressions over a regressor matrix: AutoregressionX, bgtest, bptest --------------------------------
+    @staticmethod
+    def _xreg(x, N, T):
+        """The reference's regressor matrix in the ABI's layout: x (T, k) is one matrix shared by every series, x
+        (N, T, k) one per series; None: no regressors. Returns (k rows of T values per series, x_series_stride, k)."""
+        if x is None:
+            return None, 0, 0
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim == 1:
+            x = x[:, None]
+        if x.ndim == 2 and x.shape[0] == T:
+            return np.ascontiguousarray(x.T), 0, x.shape[1]
+        if x.ndim == 3 and x.shape[:2] == (N, T):
+            return np.ascontiguousarray(x.transpose(0, 2, 1)), x.shape[2] * T, x.shape[2]
+        raise ValueError(f"x must be (T, k) or (N, T, k) with N = {N}, T = {T}; got {x.shape}")
+
+    def arx_num_coef(self, n_xcols, y_max_lag, x_max_lag, include_original_x=True):
+        K = self.L.arima_arx_num_coef(n_xcols, y_max_lag, x_max_lag, int(bool(include_original_x)))
+        if K < 0:
+            raise EngineError("arima_arx_num_coef: negative lag or column count")
+        return K
+
+    def arx_fit(self, series, x, y_max_lag, x_max_lag, include_original_x=True, no_intercept=False):
+        """AutoregressionX.fitModel of every row (AutoregressionX.scala:48-92); x (T, k) shared or (N, T, k):
+        dict(coef N x (1 + K) = (c, coefficients), status N)."""
+        series = self._rows(series)
+        N, T = series.shape
+        xr, xs, k = self._xreg(x, N, T)
+        K = self.arx_num_coef(k, y_max_lag, x_max_lag, include_original_x)
+        coef = np.empty((N, 1 + K))
+        status = np.empty(N, dtype=np.int32)
+        self._check(self.L.arima_arx_fit_batch(self.h, _ptr(series), N, T, _ptr(xr), xs, k, y_max_lag, x_max_lag,
+                                               int(bool(include_original_x)), int(bool(no_intercept)), _ptr(coef),
+                                               _ptr(status, _i32p)), "arima_arx_fit_batch")
+        return dict(coef=coef, status=status)
+
+    def arx_predict(self, series, x, y_max_lag, x_max_lag, include_original_x, coef):
+        """ARXModel.predict of every row (:117-130); coef (1 + K,) or (N, 1 + K) = (c, coefficients):
+        (N, T - max(y_max_lag, x_max_lag))."""
+        series = self._rows(series)
+        N, T = series.shape
+        xr, xs, k = self._xreg(x, N, T)
+        K = self.arx_num_coef(k, y_max_lag, x_max_lag, include_original_x)
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64).reshape(-1, 1 + K), (N, 1 + K)))
+        out = np.empty((N, max(T - max(y_max_lag, x_max_lag), 0)))
+        self._check(self.L.arima_arx_predict_batch(self.h, _ptr(series), N, T, _ptr(xr), xs, k, y_max_lag, x_max_lag,
+                                                   int(bool(include_original_x)), _ptr(coef), _ptr(out)),
+                    "arima_arx_predict_batch")
+        return out
+
+    def _regress_test(self, name, residuals, factors, *lag):
+        residuals = self._rows(residuals)
+        N, T = residuals.shape
+        xr, xs, k = self._xreg(factors, N, T)
+        r = dict(stat=np.empty(N), pvalue=np.empty(N), status=np.empty(N, dtype=np.int32))
+        self._check(getattr(self.L, name)(self.h, _ptr(residuals), N, T, _ptr(xr), xs, k, *lag, _ptr(r["stat"]),
+                                          _ptr(r["pvalue"]), _ptr(r["status"], _i32p)), name)
+        return r
+
+    def bgtest(self, residuals, factors, max_lag):
+        """TimeSeriesStatisticalTests.bgtest (TimeSeriesStatisticalTests.scala:276-288) of every row; factors (T, k)
+        shared or (N, T, k): dict(stat N, pvalue N, status N)."""
+        return self._regress_test("arima_bgtest_batch", residuals, factors, int(max_lag))
+
+    def bptest(self, residuals, factors):
+        """TimeSeriesStatisticalTests.bptest (:320-329) of every row: dict(stat N, pvalue N, status N)."""
+        return self._regress_test("arima_bptest_batch", residuals, factors)
+
+    def arx_fit_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, y_max_lag, x_max_lag,
+                       include_original_x, no_intercept, d_coef, d_status, stream=None, blocking=True):
+        """Device-pointer AutoregressionX fits (ints = raw HBM addresses); d_xreg per series n_xcols rows of T values,
+        x_series_stride 0 = shared; d_coef N x (1 + K)."""
+        self._check(self.L.arima_arx_fit_batch_device(self.h, d_series, n_series, T, ld, d_xreg, x_series_stride,
+                                                      n_xcols, y_max_lag, x_max_lag, int(bool(include_original_x)),
+                                                      int(bool(no_intercept)), d_coef, d_status, stream),
+                    "arima_arx_fit_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def arx_predict_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, y_max_lag, x_max_lag,
+                           include_original_x, d_coef, d_out, ld_out, stream=None, blocking=True):
+        """Device-pointer ARXModel.predict; d_out N x (T - maxLag) with row stride ld_out."""
+        self._check(self.L.arima_arx_predict_batch_device(self.h, d_series, n_series, T, ld, d_xreg, x_series_stride,
+                                                          n_xcols, y_max_lag, x_max_lag,
+                                                          int(bool(include_original_x)), d_coef, d_out, ld_out, stream),
+                    "arima_arx_predict_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def bgtest_device(self, d_residuals, n_series, T, ld, d_factors, x_series_stride, n_xcols, max_lag, d_stat,
+                      d_pvalue, d_status, stream=None, blocking=True):
+        """Device-pointer bgtest (ints = raw HBM addresses)."""
+        self._check(self.L.arima_bgtest_batch_device(self.h, d_residuals, n_series, T, ld, d_factors, x_series_stride,
+                                                     n_xcols, max_lag, d_stat, d_pvalue, d_status, stream),
+                    "arima_bgtest_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def bptest_device(self, d_residuals, n_series, T, ld, d_factors, x_series_stride, n_xcols, d_stat, d_pvalue,
+                      d_status, stream=None, blocking=True):
+        """Device-pointer bptest (ints = raw HBM addresses)."""
+        self._check(self.L.arima_bptest_batch_device(self.h, d_residuals, n_series, T, ld, d_factors, x_series_stride,
+                                                     n_xcols, d_stat, d_pvalue, d_status, stream),
+                    "arima_bptest_batch_device")
         if blocking:
             self.synchronize()
 
