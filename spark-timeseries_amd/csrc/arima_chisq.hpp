@@ -13,6 +13,7 @@
 //     fp64 up to a = 8), so that is what is evaluated here. Above 8 it is the library's Lanczos sum.
 //   - where the library throws (a statistic of +Inf makes the continued fraction NaN), a batch cannot: the p-value of
 //     that row is NaN. NaN in gives NaN out, as in the library.
+// The tolerance is 2.31e-14 up to L = 40 and 2.21e-13 above (measured up to L = 255).
 #pragma once
 
 #include <math.h>

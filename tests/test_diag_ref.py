@@ -94,6 +94,46 @@ def test_pvalue_restatement_against_torch_gammaincc():
     assert worst <= 1e-10
 
 
+def test_pvalue_restatement_against_mpmath_above_40_lags():
+    # The figure above was measured up to L = 40. For the larger L the device is tested at (tests/test_gpu_pvalue.py)
+    # the restatement is measured against the exact tail (mpmath at 50 digits) at that test's own statistics, a grid
+    # over the bulk and both tails, and the three doubles around the branch point stat = L + 2; the device tolerance
+    # P_TOL_ABOVE_40 of that module is 4 x the figure printed last.
+    import pvalue_cases as PC
+    worst = 0.0
+    for lag in PC.MEASURED_L:
+        stats = PC.measured_statistics(lag)
+        dist = np.abs(np.array([R.chisq_upper_tail(lag, float(s)) for s in stats]) - PC.exact_tail(lag, stats))
+        i = int(np.argmax(dist))
+        print(f"L = {lag}: largest |p - exact| over {len(stats)} statistics: {dist[i]:.3e} at stat = {float(stats[i])!r}")
+        worst = max(worst, float(dist[i]))
+    print(f"largest |p - exact| over L in {PC.MEASURED_L}: {worst:.3e}")
+    assert worst <= 1e-10                                         # the cap of the test above
+
+
+def test_pvalue_header_on_the_host_equals_the_restatement_bit_for_bit():
+    # csrc/arima_chisq.hpp compiled for the host goes through the same libm exp and log as the restatement, so there
+    # the two agree to the bit: every L up to 41 (the closed-form logGamma up to 16, Lanczos from 17) and the larger L
+    # of the device test, statistics through both branches and exactly at, just below and just above the branch point
+    # stat = L + 2, and the special values. A branch taken at another point or logGamma in another form moves a
+    # p-value by less than the device tolerance; it does not survive this.
+    import struct
+    sim = os.path.join(ROOT, "tests", "sim")
+    subprocess.run(["make", "-s", "-C", sim, "-f", "chisq.mk", "chisq"], check=True)
+    pairs = []
+    for lag in list(range(1, 42)) + [64, 127, 255]:
+        edge = [np.nextafter(lag + 2.0, 0.0), lag + 2.0, np.nextafter(lag + 2.0, np.inf)]
+        special = [0.0, -1.0, 1e300, float("inf"), float("-inf"), float("nan")]
+        pairs += [(lag, float(s)) for s in list(np.logspace(-3, np.log10(300 + 4 * lag), 60)) + edge + special]
+    text = "".join(f"{lag} {struct.unpack('<Q', struct.pack('<d', s))[0]:x}\n" for lag, s in pairs)
+    out = subprocess.run([os.path.join(sim, "_build", "chisq_host")], input=text, capture_output=True, text=True,
+                         check=True, timeout=120).stdout.split()
+    assert len(out) == len(pairs)
+    for (lag, s), word in zip(pairs, out):
+        got, ref = struct.unpack("<d", struct.pack("<Q", int(word, 16)))[0], R.chisq_upper_tail(lag, s)
+        assert (got != got and ref != ref) or struct.pack("<d", got) == struct.pack("<d", ref), (lag, s, got, ref)
+
+
 def test_pvalue_special_values():
     assert np.isnan(R.chisq_upper_tail(3, float("nan")))
     assert R.chisq_upper_tail(3, 0.0) == 1.0 and R.chisq_upper_tail(3, -5.0) == 1.0

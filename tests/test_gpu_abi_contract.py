@@ -14,10 +14,11 @@ import numpy as np
 import pytest
 
 import oracle as O
+import regress_ref as RR
 import smallfit_ref as R
 import sparkts_amd._lib as L
 from test_gpu_autofit import check_autofit
-from test_gpu_diag import _check as diag_check, _ref as diag_ref
+from test_gpu_diag import _check as diag_check, _p_close, _ref as diag_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -54,7 +55,7 @@ UNCHECKED = (DEVICE, "invalid argument")
 
 def spec(fn, device, args, faults, null=(INVALID, "null buffer"), overlap=None, n0=(OK, MARK), zero=(), alias_in=None):
     """faults: (label, scalar overrides, rc, message); null: what a null required buffer returns; overlap: the message of a refused overlap (None: the entry point
-    does not look); n0: what N = 0 with every buffer null returns; zero: overrides of further early-OK calls;
+    does not look), or the pair of messages (an output on an input, an output on another output); n0: what N = 0 with every buffer null returns; zero: overrides of further early-OK calls;
     alias_in: the input an output may alias exactly (the overlap rows shift that output by one element)."""
     return NS(fn=fn, device=device, args=args, faults=faults, null=null, overlap=overlap, n0=n0, zero=zero,
               alias_in=alias_in)
@@ -142,6 +143,59 @@ def _model_specs():
     return out
 
 
+# The regressions over a regressor matrix: k = 2 columns, AutoregressionX(yMaxLag 1, xMaxLag 1, includeOriginalX) has
+# K = 5 predictors and R = 11 rows, bgtest max_lag 3. The faults in the order regress_check and its callers test them.
+RG = NS(k=2, yl=1, xl=1, K=5, R=S.T - 1, xs_h=2 * S.T, xs_d=2 * S.T + 4, ldo=S.T + 2)
+RG_OVERLAP = ("an output overlaps an input", "outputs overlap")       # check_overlap's two messages, passed through
+
+
+def _regress_specs():
+    out = []
+    for device in (False, True):
+        sfx, xs = ("_device", RG.xs_d) if device else ("", RG.xs_h)
+        head = [B("rows", "in", ROWS_D if device else ROWS_H), V("N", S.N), V("T", S.T)] + \
+            ([V("ld", S.ld)] if device else []) + \
+            [B("xreg", "in", ((S.N - 1) * xs + RG.k * S.T) * 8), V("xs", xs), V("k", RG.k)]
+        tail = [V("stream", None)] if device else []
+        shape = [("N < 0", dict(N=-1), INVALID, "bad shape"), ("T < 0", dict(T=-1), INVALID, "bad shape")] + \
+            ([("ld < T", dict(ld=S.T - 1), INVALID, "bad shape")] if device else []) + \
+            [("n_xcols < 0", dict(k=-1), INVALID, "bad shape")]
+        stride = [("x_series_stride below n_xcols * T", dict(xs=RG.k * S.T - 1), INVALID,
+                   "x_series_stride below n_xcols * T")]
+        lags = [("y_max_lag < 0", dict(yl=-1), INVALID, "bad shape"), ("x_max_lag < 0", dict(xl=-1), INVALID, "bad shape")]
+        wide = "at most 64 columns"
+        arx = [V("yl", RG.yl), V("xl", RG.xl), V("orig", 1)]
+        out.append(spec("arima_arx_fit_batch" + sfx, device,
+                        head + arx + [V("noint", 0), B("coef", "out", ND * (1 + RG.K)), B("status", "out", NI)] + tail,
+                        shape + lags + stride +
+                        [("the stride before the columns", dict(xs=RG.k * S.T - 1, yl=62), INVALID, stride[0][3]),
+                         ("65 columns", dict(yl=62), UNSUPPORTED, wide),                  # 1 + 62 + 2
+                         ("65 columns before N = 0", dict(yl=62, N=0), UNSUPPORTED, wide)],
+                        overlap=RG_OVERLAP))
+        out.append(spec("arima_arx_predict_batch" + sfx, device,
+                        head + arx + [B("coef", "in", ND * (1 + RG.K)),
+                                      B("out", "out", ((S.N - 1) * RG.ldo + RG.R) * 8 if device else ND * RG.R)] +
+                        ([V("ldo", RG.ldo)] if device else []) + tail,
+                        shape + lags + stride +
+                        [("65 predictors", dict(yl=61), UNSUPPORTED, wide),               # no ones column: 61 + 2 + 2
+                         ("T < maxLag", dict(yl=S.T + 1), INVALID, "bad shape")] +
+                        ([("ld_out < R", dict(ldo=RG.R - 1), INVALID, "bad shape")] if device else []),
+                        overlap=RG_OVERLAP, zero=[dict(T=1)]))                            # R = 0: nothing to predict
+        test_outs = [B("stat", "out", ND), B("pvalue", "out", ND), B("status", "out", NI)]
+        out.append(spec("arima_bgtest_batch" + sfx, device, head + [V("lag", S.lag)] + test_outs + tail,
+                        shape + [("max_lag < 0", dict(lag=-1), INVALID, "bad shape"),
+                                 ("bad shape before max_lag 0", dict(lag=0, N=-1), INVALID, "bad shape"),
+                                 ("max_lag 0", dict(lag=0), INVALID, "max_lag < 1"),
+                                 ("max_lag 0 before the stride", dict(lag=0, xs=1), INVALID, "max_lag < 1")] + stride +
+                        [("65 columns", dict(lag=62), UNSUPPORTED, wide)],                # 1 + 2 + 62
+                        overlap=RG_OVERLAP))
+        out.append(spec("arima_bptest_batch" + sfx, device, head + test_outs + tail,
+                        shape + [("n_xcols 0", dict(k=0), INVALID, "n_xcols < 1")] + stride +
+                        [("65 columns", dict(k=64, xs=0), UNSUPPORTED, wide)],            # 1 + 64, one shared matrix
+                        overlap=RG_OVERLAP))
+    return out
+
+
 SEARCH = [V("max_p", 2), V("max_d", 1), V("max_q", 2), V("imode", 2), V("method", 0)]
 SEARCH_OUT = [B("order", "out", S.N * 16), B("coef11", "out", S.N * 88), B("aic", "out", ND)]
 AUTOFIT_OUT = SEARCH_OUT + [B("status", "out", NI), B("n_fits", "out", NI, False)]
@@ -219,7 +273,7 @@ SPECS = [
           ("max_d > 16", dict(max_d=17), UNSUPPORTED, AF_UNSUPPORTED),
           ("N < 0", dict(N=-1), INVALID, "bad shape"), ("T < 0", dict(T=-1), INVALID, "bad shape"),
           ("ld < T", dict(ld=S.T - 1), INVALID, "bad shape")], null=(INVALID, "bad shape")),
-] + _effects_specs() + _diag_specs() + _model_specs()
+] + _effects_specs() + _diag_specs() + _model_specs() + _regress_specs()
 
 
 def rows_of(sp):
@@ -233,10 +287,11 @@ def rows_of(sp):
     t.append(("N = 0, every buffer null", dict(N=0), {a.name: None for a in bufs}, *sp.n0))
     t += [(f"early OK {ov}", ov, {}, OK, MARK) for ov in sp.zero]
     if sp.overlap:
+        on_in, on_out = sp.overlap if isinstance(sp.overlap, tuple) else (sp.overlap, sp.overlap)
         for i, o in enumerate(outs):
             t += [(f"{o.name} on {a.name}", {}, {o.name: (a.name, 8 if a.name == sp.alias_in else 0)}, INVALID,
-                   sp.overlap) for a in ins]
-            t += [(f"{o.name} on {o2.name}", {}, {o.name: (o2.name, 0)}, INVALID, sp.overlap) for o2 in outs[i + 1:]]
+                   on_in) for a in ins]
+            t += [(f"{o.name} on {o2.name}", {}, {o.name: (o2.name, 0)}, INVALID, on_out) for o2 in outs[i + 1:]]
     if sp.alias_in and sp.device:
         t.append(("out on the rows, another stride", dict(ldo=S.ld + 1), {"out": (sp.alias_in, 0)}, INVALID, sp.overlap))
     return t
@@ -485,9 +540,25 @@ def fam_model_effects(e, N):
     assert _same(e.garch_add_effects(s, GC[:N]), np.array([R.garch_add(r, *c) for r, c in zip(rows, g)]))
 
 
+def fam_regress(e, N):
+    s, _ = _data(N)
+    x = np.random.default_rng(20261021).standard_normal((5, S.T, RG.k))[:N]
+    fits = [RR.arx_fit(s[i], x[i].T, RG.yl, RG.xl, True, False) for i in range(N)]
+    coef = np.array([[c] + list(cf) for _, c, cf in fits])
+    got = e.arx_fit(s, x, RG.yl, RG.xl, True, False)
+    assert np.all(got["status"] == RR.ST_OK) and np.array_equal(got["status"], [f[0] for f in fits])
+    assert coef.shape == (N, 1 + RG.K) and _same(got["coef"], coef)
+    pred = np.array([RR.arx_predict(s[i], x[i].T, coef[i, 0], coef[i, 1:], RG.yl, RG.xl, True) for i in range(N)])
+    assert pred.shape == (N, RG.R) and _same(e.arx_predict(s, x, RG.yl, RG.xl, True, coef), pred)
+    for got, ref in ((e.bgtest(s, x, S.lag), [RR.bgtest(s[i], x[i].T, S.lag) for i in range(N)]),
+                     (e.bptest(s, x), [RR.bptest(s[i], x[i].T) for i in range(N)])):
+        assert np.all(got["status"] == RR.ST_OK) and np.array_equal(got["status"], [r[0] for r in ref])
+        assert _same(got["stat"], np.array([r[1] for r in ref])) and _p_close(got["pvalue"], [r[2] for r in ref])
+
+
 FAMILIES = [fam_difference, fam_css_loglik, fam_css_gradient, fam_hannan_rissanen, fam_model_flags, fam_forecast,
             fam_effects, fam_diagnostics, fam_residual_diagnostics, fam_order_search, fam_autofit, fam_kpss,
-            fam_model_fit, fam_model_eval, fam_model_effects]
+            fam_model_fit, fam_model_eval, fam_model_effects, fam_regress]
 
 
 @pytest.fixture

@@ -27,13 +27,15 @@ import pytest
 
 import argarch_ref as AR
 import oracle as O
+import regress_ref as RR
 import smallfit_ref as SR
 import sparkts_amd._lib as L
 from conftest import load_case
 from test_gpu_autofit import check_autofit
-from test_gpu_diag import _check as diag_check, _ref as diag_ref
+from test_gpu_diag import _check as diag_check, _p_close, _ref as diag_ref
 from test_gpu_hostpath import C1, C2, _c2_T100, device_fit, identical, oracle_fit, plan, sample_rows, sampled, take
 from test_gpu_parity import _device_sample, _same, check_fit
+from test_gpu_regress import _arx_case
 
 pytestmark = pytest.mark.gpu
 
@@ -41,7 +43,7 @@ SENT, ISENT, BSENT = -7.25, -77, 0xEE
 G = 8                                   # guard rows before and after every output
 DELAY_TARGET_MS, DELAY_MIN_MS = 50.0, 20.0
 DELAY_DOUBLES = 1 << 26                 # 512 MiB scaled in place per launch
-OPTIONS = ("fit_pipeline", "search_lanes", "fit_slice_bytes", "diag_slice_bytes", "autofit_slice")
+OPTIONS = ("fit_pipeline", "search_lanes", "fit_slice_bytes", "diag_slice_bytes", "autofit_slice", "regress_slice_bytes")
 JOIN_S = 120
 
 _memo = {}
@@ -592,6 +594,75 @@ def pair_case(kind, arg, direction=None):
     return build
 
 
+RG_N, RG_T, RG_LAG = 70, 40, 2
+RG_CFG = (3, 2, 3, True, False)         # yMaxLag, xMaxLag, k, includeOriginalX, noIntercept: K = 12, R = 37
+
+
+def _regress_inputs():
+    """70 rows of tests/test_gpu_regress.py's batch of RG_CFG with its restated fits and predictions, the restated
+    bgtest and bptest of the same rows, and decoys. x: per series k rows of T values."""
+    def make():
+        k = RG_CFG[2]
+        y, x, coef, status, pred = (a[:RG_N] for a in _arx_case(RG_CFG))
+        rng = np.random.default_rng(440)
+        return dict(y=y, x=np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(RG_N, k * RG_T), coef=coef, status=status,
+                    pred=pred, bg=[RR.bgtest(y[i], x[i].T, RG_LAG) for i in range(RG_N)],
+                    bp=[RR.bptest(y[i], x[i].T) for i in range(RG_N)], decoy_y=_walks(441, RG_N, RG_T),
+                    decoy_x=rng.standard_normal((RG_N, k * RG_T)), decoy_coef=rng.uniform(-0.5, 0.5, coef.shape))
+    return memo("regress_inputs", make)
+
+
+def _regress_sources(dev, r):
+    """The rows (ld = T + 3) and the regressors (a series stride of k T + 5) and the arguments that name them."""
+    k = RG_CFG[2]
+    d_y, d_x = In(dev, r["y"], r["decoy_y"], ld=RG_T + 3), In(dev, r["x"], r["decoy_x"], ld=k * RG_T + 5)
+    return d_y, d_x, (d_y.ptr, RG_N, RG_T, d_y.ld, d_x.ptr, d_x.ld, k)
+
+
+def regress_case(which):
+    """which: arx_fit, arx_predict, bgtest or bptest."""
+    def build(engine, dev):
+        r = _regress_inputs()
+        yl, xl, k, orig, noint = RG_CFG
+        d_y, d_x, head = _regress_sources(dev, r)
+        if which == "arx_fit":
+            outs = [Out(dev, RG_N, 1 + yl + k * xl + k), Out(dev, RG_N, dtype="int32")]
+
+            def call(stream):
+                engine.arx_fit_device(*head, yl, xl, orig, noint, *ptrs(outs), stream=stream, blocking=False)
+
+            def check(got):
+                same(got[0], r["coef"], "arx fit coef")
+                same(got[1], r["status"], "arx fit status")
+
+            return Scenario([d_y, d_x], outs, call, check)
+        if which == "arx_predict":
+            d_coef = In(dev, r["coef"], r["decoy_coef"])
+            rows = RG_T - max(yl, xl)
+            out = Out(dev, RG_N, rows, ld=rows + 5)
+
+            def call(stream):
+                engine.arx_predict_device(*head, yl, xl, orig, d_coef.ptr, out.ptr, out.ld, stream=stream, blocking=False)
+
+            return Scenario([d_y, d_x, d_coef], [out], call, lambda got: same(got[0], r["pred"], "arx predict"))
+        outs = [Out(dev, RG_N), Out(dev, RG_N), Out(dev, RG_N, dtype="int32")]
+        ref = r["bg" if which == "bgtest" else "bp"]
+
+        def call(stream):
+            if which == "bgtest":
+                engine.bgtest_device(*head, RG_LAG, *ptrs(outs), stream=stream, blocking=False)
+            else:
+                engine.bptest_device(*head, *ptrs(outs), stream=stream, blocking=False)
+
+        def check(got):
+            same(got[0], np.array([x[1] for x in ref]), f"{which} statistic")
+            assert _p_close(got[1], [x[2] for x in ref]), f"{which} p-value"
+            same(got[2], np.array([x[0] for x in ref], dtype=np.int32), f"{which} status")
+
+        return Scenario([d_y, d_x], outs, call, check)
+    return build
+
+
 def _cases():
     c = []
     for model in FIT_MODELS:
@@ -619,6 +690,10 @@ def _cases():
             c.append(pytest.param(pair_case("ar", p, direction), {}, id=f"ar_{direction}_effects-p{p}"))
     for model in ("garch", "argarch"):
         c.append(pytest.param(pair_case("sample", model), {}, id=f"{model}_sample"))
+    for which in ("arx_fit", "arx_predict"):
+        c.append(pytest.param(regress_case(which), {}, id=which))
+    for which in ("bgtest", "bptest"):                         # 70 series in slices of 64: the slice loop on the caller's stream
+        c.append(pytest.param(regress_case(which), dict(regress_slice_bytes=1), id=f"{which}-2-slices"))
     return c
 
 
@@ -821,6 +896,38 @@ def test_ar_residuals_then_garch_fit_across_streams(engine, rig):
     for g, k in zip(got[1:], MODEL_KEYS):
         same(g, serial["fit"][k], f"GARCH fit {k}")
         same(g, want[k], f"GARCH part of the fused fit {k}")
+    s1.synchronize()
+
+
+def test_arx_fit_then_predict_across_streams(engine, rig):
+    # non-fit -> non-fit: the regression writes its coefficients on one stream, ARXModel.predict reads them on another
+    torch = rig.torch
+    r = _regress_inputs()
+    yl, xl, k, orig, noint = RG_CFG
+    d_y, d_x, head = _regress_sources(rig.dev, r)
+    rows = RG_T - max(yl, xl)
+    f_outs = [Out(rig.dev, RG_N, 1 + yl + k * xl + k), Out(rig.dev, RG_N, dtype="int32")]
+    pred = Out(rig.dev, RG_N, rows, ld=rows + 5)
+    s1, s2 = rig.chain(1, 2)
+    torch.cuda.synchronize(rig.dev)
+    with torch.cuda.stream(s1):
+        rig.delay()
+        d_y.load()
+        d_x.load()
+        engine.arx_fit_device(*head, yl, xl, orig, noint, *ptrs(f_outs), stream=s1.cuda_stream, blocking=False)
+    with torch.cuda.stream(s2):
+        engine.arx_predict_device(*head, yl, xl, orig, f_outs[0].ptr, pred.ptr, pred.ld, stream=s2.cuda_stream,
+                                  blocking=False)
+        outs = f_outs + [pred]
+        snaps, in_snaps = snapshots(outs), snapshots([d_y, d_x])
+    s2.synchronize()
+    got = bodies(rig, s2, outs, snaps, "arx fit -> predict")
+    same(got[0], r["coef"], "the fit's coefficients")
+    same(got[1], r["status"], "the fit's status")
+    assert np.all(r["status"] == RR.ST_OK)
+    same(got[2], r["pred"], "the prediction at the fit's coefficients")        # regress_ref's, at the real coefficients
+    for i, x in zip((d_y, d_x), in_snaps):
+        i.untouched(rig.host(x, s2), "arx fit -> predict")
     s1.synchronize()
 
 
