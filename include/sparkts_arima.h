@@ -322,6 +322,34 @@ int arima_bgtest_batch_device(arima_handle *h, const double *d_residuals, int64_
 int arima_bptest_batch_device(arima_handle *h, const double *d_residuals, int64_t n_series, int32_t T, int64_t ld,
                               const double *d_factors, int64_t x_series_stride, int32_t n_xcols, double *d_stat_out,
                               double *d_pvalue_out, int32_t *d_status_out, void *stream);
+/* ---- RegressionARIMA.fitModel("cochrane-orcutt") over a batch (RegressionARIMA.scala:83-176) ---------------------- *
+ * A regression of y on the regressor matrix with an intercept and AR(1) errors, by the iterated Cochrane-Orcutt
+ * procedure, in the reference's arithmetic and order: every output is bit-identical to tests/regarima_ref.py.
+ * series N x T; xreg and x_series_stride as for the arx entry points (per series n_xcols rows of T values, 0 = shared).
+ * Per series: OLS of y on [1, X] (the QR above); while the Durbin-Watson statistic of the last regression's residuals
+ * is outside (2 - 0.05, 2 + 0.05): rho = the no-intercept slope of res(t + 1) on res(t) (SimpleRegression(false));
+ * OLS of y(t) - rho y(t-1) on [1, X(t, .) - rho X(t-1, .)] over T - 1 rows; beta(0) /= 1 - rho; res = y - (X beta +
+ * beta(0)); until max_iter iterations have run or two successive rho differ by at most 0.001. SimpleRegression's sums
+ * and dgemv's order are unpinned readings.
+ * coef_out N x (1 + n_xcols) = regressionCoeff (intercept first); rho_out N = arimaCoeff(0), 0.0 for a series that
+ * never iterated (arimaOrders is (1, 0, 0)); n_iter_out N (nullable): the iterations run, also for a failed series.
+ * status_out N carries what the reference throws, per series: ARIMA_ST_NO_DATA (T == 0), ARIMA_ST_NOT_ENOUGH_DATA
+ * (n_xcols + 1 > T at the first regression, n_xcols + 1 > T - 1 at a transformed one), ARIMA_ST_SINGULAR (an rDiag of
+ * either QR exactly 0); a failed series has NaN coef and rho and never aborts the batch. NaN and Inf propagate as in
+ * the JVM: a NaN rho gives NaN coefficients with status OK, and the NaN Durbin-Watson statistic ends the loop.
+ * max_iter < 1 (the reference throws on every path), n_xcols < 1, T < 0 and an x_series_stride in (0, n_xcols * T)
+ * return ARIMA_E_INVALID_ARG; more than 64 design columns (the ones column included) return ARIMA_E_UNSUPPORTED;
+ * N == 0 returns ARIMA_OK and writes nothing. Outputs that overlap an input or one another return
+ * ARIMA_E_INVALID_ARG. The whole iteration of a series runs in one kernel; a slice of series needs about
+ * (2 n_xcols + 3) T doubles each in the workspace of "regress_slice_bytes", and results never depend on the slices. */
+int arima_regarima_co_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T,
+                                const double *xreg, int64_t x_series_stride, int32_t n_xcols, int32_t max_iter,
+                                double *coef_out, double *rho_out, int32_t *n_iter_out, int32_t *status_out);
+/* Same, device-resident: d_series N x T (row stride ld >= T, else ARIMA_E_INVALID_ARG)                           */
+int arima_regarima_co_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T,
+                                       int64_t ld, const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
+                                       int32_t max_iter, double *d_coef_out, double *d_rho_out,
+                                       int32_t *d_n_iter_out, int32_t *d_status_out, void *stream);
 /* ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815) for N coefficient rows, flags_out N */
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t n_series, int32_t p, int32_t q,
                             int32_t include_intercept, uint8_t *flags_out);

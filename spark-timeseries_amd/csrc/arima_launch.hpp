@@ -62,7 +62,7 @@ int launch_garch_sample(int model, const double *z, int64_t ld_in, const double 
 // commons' OLSMultipleLinearRegression over a design that is not made only of a series' own lags. A design has R rows
 // and C columns (the ones column included); every column is a window of one source row: value(r) = source[off + r].
 constexpr int kRgMaxCols = 64;     // C of k_regress_qr
-constexpr int kRgArx = 0, kRgBg = 1, kRgBp = 2;
+constexpr int kRgArx = 0, kRgBg = 1, kRgBp = 2, kRgCo = 3;
 // RgCol::src: literal 1.0, the per-series row; j >= 0: regressor column j
 constexpr int kRgOnes = -2, kRgSelf = -1;
 struct RgCol {
@@ -70,8 +70,9 @@ struct RgCol {
     bool sq;                                       // the value squared (bptest's response)
 };
 // kind kRgArx: AutoregressionX.fitModel(y, x, lag_a = yMaxLag, lag_b = xMaxLag, orig = includeOriginalX, icpt =
-// !noIntercept); kRgBg: bgtest(residuals, factors, lag_a = maxLag); kRgBp: bptest(residuals, factors). T values per
-// row, k regressor columns
+// !noIntercept); kRgBg: bgtest(residuals, factors, lag_a = maxLag); kRgBp: bptest(residuals, factors); kRgCo: the
+// pristine copy of RegressionARIMA.fitCochraneOrcutt(y, x), bptest's rows with the response not squared and no ones
+// column (icpt = 0). T values per row, k regressor columns
 struct RgDesign {
     int kind, T, k, lag_a, lag_b, orig, icpt;
     __host__ __device__ int max_lag() const {
@@ -125,6 +126,13 @@ int launch_regress_r2(const double *ws, const double *beta, const int32_t *statu
 // ARXModel.predict straight from the sources: coef N x (1 + K) = (c, coefficients), out N x rows() (row stride ld_out)
 int launch_arx_predict(const RgDesign &d, const RgSrc &src, const double *coef, double *out, int64_t ld_out, int64_t N,
                        hipStream_t s);
+// RegressionARIMA.fitCochraneOrcutt, the whole iteration of every series in one launch. ps: the kRgCo design of the n
+// series as launch_regress_assemble wrote it (rg_ws_doubles(n, T, k) doubles: x_0 .. x_{k-1}, then y), read only; wk:
+// rg_ws_doubles(n, T, k + 1) doubles of working design, rebuilt and destroyed once per QR. coef_out N x (1 + k)
+// (intercept first), rho_out N, n_iter_out N (nullable): the iterations run, also for a failed series; status_out N.
+// Needs 1 <= k, k + 1 <= T and k + 1 <= kRgMaxCols (the entry points report every other shape)
+int launch_cochrane_orcutt(const double *ps, double *wk, int64_t N, int T, int k, int max_iter, double *coef_out,
+                           double *rho_out, int32_t *n_iter_out, int32_t *status_out, hipStream_t s);
 // a shape the reference refuses for every series alike: status to status_out, NaN to the n0 / n1 doubles per series
 // of out0 / out1 (null: none)
 int launch_regress_refuse(int64_t N, int32_t status, int32_t *status_out, double *out0, int n0, double *out1, int n1,

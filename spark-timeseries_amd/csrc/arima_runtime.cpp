@@ -1879,6 +1879,102 @@ int arima_bptest_batch_device(arima_handle *h, const double *d_residuals, int64_
                           nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
 }
 
+// RegressionARIMA.fitCochraneOrcutt (RegressionARIMA.scala:83-160): regress_check's rules on the pristine-copy design,
+// then its own
+namespace {
+int co_check(arima_handle *h, const RgDesign &d, int64_t N, int64_t ld, int64_t xs, int32_t max_iter, bool *done) {
+    *done = false;
+    // new Array(maxIter) or rhos(0) throws; the zero-column dgemv is unread
+    if (max_iter < 1) return set_err(h, ARIMA_E_INVALID_ARG, "max_iter < 1");
+    if (d.k < 1) return set_err(h, ARIMA_E_INVALID_ARG, "n_xcols < 1");
+    PASSCHK(regress_check(h, d, N, ld, xs, done));
+    if (d.num_pred() + 1 > sts::kRgMaxCols) return set_err(h, ARIMA_E_UNSUPPORTED, "at most 64 columns");
+    return ARIMA_OK;
+}
+
+// Slice by slice: the pristine copy of y and X, then the whole iteration in one launch. A slice's workspace is the
+// copy ((k + 1) T doubles per series) and the working design ((k + 2) T) behind it.
+int co_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N, int32_t max_iter, double *coef_out,
+           double *rho_out, int32_t *n_iter_out, int32_t *status_out, hipStream_t s) {
+    const int k = d.k, T = d.T;
+    // step 1's OLSMultipleLinearRegression.validateSampleData, the same for every series of the call
+    const int32_t shape = T == 0 ? ARIMA_ST_NO_DATA : k + 1 > T ? ARIMA_ST_NOT_ENOUGH_DATA : ARIMA_ST_OK;
+    if (shape != ARIMA_ST_OK) {
+        RCCHK(h, sts::launch_regress_refuse(N, shape, status_out, coef_out, 1 + k, rho_out, 1, s), "regression");
+        if (n_iter_out) HIPCHK(h, hipMemsetAsync(n_iter_out, 0, (size_t)N * sizeof(int32_t), s));
+        return ARIMA_OK;
+    }
+    int64_t slice_bytes = h->regress_slice_bytes;
+    if (slice_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
+    }
+    const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, (int64_t)(2 * k + 3) * T);
+    const int64_t copy_doubles = sts::rg_ws_doubles(std::min(slice, N), T, k);
+    RCCHK(h, h->rg_ws.ensure((size_t)(copy_doubles + sts::rg_ws_doubles(std::min(slice, N), T, k + 1)) *
+                             sizeof(double)), "regression workspace");
+    double *ps = h->rg_ws.as<double>(), *wk = ps + copy_doubles;
+    for (int64_t f = 0; f < N; f += slice) {
+        const int64_t n = std::min(slice, N - f);
+        RCCHK(h, sts::launch_regress_assemble(d, src.at(f), n, ps, s), "design");
+        RCCHK(h, sts::launch_cochrane_orcutt(ps, wk, n, T, k, max_iter, coef_out + f * (1 + k), rho_out + f,
+                                             n_iter_out ? n_iter_out + f : nullptr, status_out + f, s),
+              "cochrane-orcutt");
+    }
+    return ARIMA_OK;
+}
+}  // namespace
+
+int arima_regarima_co_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
+                                int64_t x_series_stride, int32_t n_xcols, int32_t max_iter, double *coef_out,
+                                double *rho_out, int32_t *n_iter_out, int32_t *status_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kHostBuffers);
+    const RgDesign d{sts::kRgCo, T, n_xcols, 0, 0, 0, 0};
+    bool done;
+    PASSCHK(co_check(h, d, N, T, x_series_stride, max_iter, &done));
+    if (done) return ARIMA_OK;
+    if (regress_null_input(d, {series, T, xreg, x_series_stride}) || !coef_out || !rho_out || !status_out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
+                 x_bytes = (size_t)regress_x_doubles(d, N, x_series_stride) * sizeof(double),
+                 coef_bytes = nd * (1 + (size_t)n_xcols), ni = (size_t)N * sizeof(int32_t);
+    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes)},
+                          {ByteSpan(coef_out, coef_bytes), ByteSpan(rho_out, nd),
+                           ByteSpan(n_iter_out, n_iter_out ? ni : 0), ByteSpan(status_out, ni)}));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_out(coef_out, coef_bytes),
+                     stage_out(rho_out, nd), stage_optional_out(n_iter_out, ni), stage_out(status_out, ni)}));
+    const RgSrc src{f.dev<double>(0), T, x_bytes ? f.dev<double>(1) : nullptr, x_series_stride};
+    PASSCHK(co_dev(h, d, src, N, max_iter, f.dev<double>(2), f.dev<double>(3), f.dev<int32_t>(4), f.dev<int32_t>(5),
+                   f.s()));
+    return f.finish();
+}
+
+int arima_regarima_co_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                       const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
+                                       int32_t max_iter, double *d_coef_out, double *d_rho_out,
+                                       int32_t *d_n_iter_out, int32_t *d_status_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kDeviceBuffers);
+    const RgDesign d{sts::kRgCo, T, n_xcols, 0, 0, 0, 0};
+    bool done;
+    PASSCHK(co_check(h, d, N, ld, x_series_stride, max_iter, &done));
+    if (done) return ARIMA_OK;
+    if (regress_null_input(d, {d_series, ld, d_xreg, x_series_stride}) || !d_coef_out || !d_rho_out || !d_status_out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int64_t nd = N * (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t);
+    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
+                              ByteSpan(d_xreg, regress_x_doubles(d, N, x_series_stride) * (int64_t)sizeof(double))},
+                          {ByteSpan(d_coef_out, nd * (1 + n_xcols)), ByteSpan(d_rho_out, nd),
+                           ByteSpan(d_n_iter_out, d_n_iter_out ? ni : 0), ByteSpan(d_status_out, ni)}));
+    PASSCHK(f.begin(stream));
+    const RgSrc src{d_series, ld, (int64_t)n_xcols * T ? d_xreg : nullptr, x_series_stride};
+    PASSCHK(co_dev(h, d, src, N, max_iter, d_coef_out, d_rho_out, d_n_iter_out, d_status_out, f.s()));
+    return f.finish();
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // order search over (d, p, q, intercept) — SURVEY.md 8(f) row 2 (config C5)
 // ---------------------------------------------------------------------------------------------------------

@@ -69,7 +69,7 @@ EXPORTED = [
     "arima_argarch_sample_batch", "arima_garch_sample_batch_device", "arima_argarch_sample_batch_device",
     "arima_arx_num_coef", "arima_arx_fit_batch", "arima_arx_fit_batch_device", "arima_arx_predict_batch",
     "arima_arx_predict_batch_device", "arima_bgtest_batch", "arima_bgtest_batch_device", "arima_bptest_batch",
-    "arima_bptest_batch_device",
+    "arima_bptest_batch_device", "arima_regarima_co_fit_batch", "arima_regarima_co_fit_batch_device",
 ]
 
 # the small models (EWMA.scala, GARCH.scala): parameters per series; ARGARCH's are (c, phi, omega, alpha, beta)
@@ -218,6 +218,9 @@ def load():
         L.arima_bgtest_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp]
         L.arima_bptest_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _dp, _dp, _i32p]
         L.arima_bptest_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]
+        L.arima_regarima_co_fit_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _dp, _dp, _i32p, _i32p]
+        L.arima_regarima_co_fit_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp,
+                                                         _vp, _vp, _vp]
         _lib = L
         return L
 
@@ -729,6 +732,19 @@ class Engine:
         """TimeSeriesStatisticalTests.bptest (:320-329) of every row: dict(stat N, pvalue N, status N)."""
         return self._regress_test("arima_bptest_batch", residuals, factors)
 
+    def regarima_co_fit(self, series, x, max_iter=10):
+        """RegressionARIMA.fitCochraneOrcutt of every row (RegressionARIMA.scala:83-160); x (T, k) shared or (N, T, k):
+        dict(coef N x (1 + k) = regressionCoeff, rho N = arimaCoeff(0), n_iter N, status N)."""
+        series = self._rows(series)
+        N, T = series.shape
+        xr, xs, k = self._xreg(x, N, T)
+        r = dict(coef=np.empty((N, 1 + k)), rho=np.empty(N), n_iter=np.empty(N, dtype=np.int32),
+                 status=np.empty(N, dtype=np.int32))
+        self._check(self.L.arima_regarima_co_fit_batch(self.h, _ptr(series), N, T, _ptr(xr), xs, k, int(max_iter),
+                                                       _ptr(r["coef"]), _ptr(r["rho"]), _ptr(r["n_iter"], _i32p),
+                                                       _ptr(r["status"], _i32p)), "arima_regarima_co_fit_batch")
+        return r
+
     def arx_fit_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, y_max_lag, x_max_lag,
                        include_original_x, no_intercept, d_coef, d_status, stream=None, blocking=True):
         """Device-pointer AutoregressionX fits (ints = raw HBM addresses); d_xreg per series n_xcols rows of T values,
@@ -765,6 +781,17 @@ class Engine:
         self._check(self.L.arima_bptest_batch_device(self.h, d_residuals, n_series, T, ld, d_factors, x_series_stride,
                                                      n_xcols, d_stat, d_pvalue, d_status, stream),
                     "arima_bptest_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def regarima_co_fit_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, max_iter, d_coef,
+                               d_rho, d_n_iter, d_status, stream=None, blocking=True):
+        """Device-pointer Cochrane-Orcutt fits (ints = raw HBM addresses); d_coef N x (1 + n_xcols), d_n_iter may be
+        None."""
+        self._check(self.L.arima_regarima_co_fit_batch_device(self.h, d_series, n_series, T, ld, d_xreg,
+                                                              x_series_stride, n_xcols, int(max_iter), d_coef, d_rho,
+                                                              d_n_iter, d_status, stream),
+                    "arima_regarima_co_fit_batch_device")
         if blocking:
             self.synchronize()
 

@@ -4,3 +4,4 @@ from . import GARCH  # noqa: F401
 from . import ARGARCH  # noqa: F401
 from . import Autoregression  # noqa: F401
 from . import AutoregressionX  # noqa: F401
+from . import RegressionARIMA  # noqa: F401

@@ -3,11 +3,15 @@
   arx_shared      arima_arx_fit_batch_device, ARX(2, 1, includeOriginalX), 2 regressor columns shared by every series
   arx_per_series  the same with one regressor matrix per series
   bgtest          arima_bgtest_batch_device, max_lag 4, one factor column per series
-The three alternate in one process after a warm-up launch of each, every launch timed with a HIP event pair on the
+  co_shared       arima_regarima_co_fit_batch_device (Cochrane-Orcutt, max_iter 10), the 2 regressor columns shared
+  co_per_series   the same with one regressor matrix per series
+The five alternate in one process after a warm-up launch of each, every launch timed with a HIP event pair on the
 caller's stream; medians and spreads (max - min) are reported, with series per second and the achieved bytes per second
 against the traffic model of DESIGN.md 5.7 (2 C^2 R 8 bytes per series for the QR; the tests add their second assembly
 and the calculateRSquared pass). For context only, oracle.ols (the C restatement of the same QR) over the designs of
-the first --cpu-series series on --cpu-threads host threads. Prints one JSON line and writes it to --out.
+the first --cpu-series series on --cpu-threads host threads. The Cochrane-Orcutt legs run a data-dependent number of
+QRs per series (n_iter + 1): they report the histogram of n_iter and its mean next to series per second,
+and no traffic model. Prints one JSON line and writes it to --out.
 usage: python tools/bench_regress.py [--series N] [--launches K] [--out FILE]
 """
 import argparse
@@ -50,7 +54,9 @@ def main():
     y = (torch.randn((N, T), **f64).cumsum(1) * 0.1 + x.sum(1) + 2.0).contiguous()
     coef = [torch.empty((N, 7), **f64) for _ in range(2)]
     stat, pv = torch.empty(N, **f64), torch.empty(N, **f64)
-    st = [torch.empty(N, dtype=torch.int32, device=dev) for _ in range(3)]
+    st = [torch.empty(N, dtype=torch.int32, device=dev) for _ in range(5)]
+    co = [(torch.empty((N, 1 + k), **f64), torch.empty(N, **f64), torch.empty(N, dtype=torch.int32, device=dev))
+          for _ in range(2)]
     ts = torch.cuda.Stream()
     stream = ts.cuda_stream
     assert stream, "need a non-default stream"
@@ -63,6 +69,13 @@ def main():
                                                      blocking=False),
         "bgtest": lambda: eng.bgtest_device(y.data_ptr(), N, T, T, x.data_ptr(), k * T, 1, 4, stat.data_ptr(),
                                             pv.data_ptr(), st[2].data_ptr(), stream=stream, blocking=False),
+        "co_shared": lambda: eng.regarima_co_fit_device(y.data_ptr(), N, T, T, x.data_ptr(), 0, k, 10,
+                                                        co[0][0].data_ptr(), co[0][1].data_ptr(), co[0][2].data_ptr(),
+                                                        st[3].data_ptr(), stream=stream, blocking=False),
+        "co_per_series": lambda: eng.regarima_co_fit_device(y.data_ptr(), N, T, T, x.data_ptr(), k * T, k, 10,
+                                                            co[1][0].data_ptr(), co[1][1].data_ptr(),
+                                                            co[1][2].data_ptr(), st[4].data_ptr(), stream=stream,
+                                                            blocking=False),
     }
     shape = {"arx_shared": (7, T - 2, False), "arx_per_series": (7, T - 2, False), "bgtest": (6, T - 4, True)}
     ms = {name: [] for name in calls}
@@ -80,12 +93,17 @@ def main():
            "library_sha": buildinfo.library_sha(), "source_sha": buildinfo.source_sha()}
     for name, v in ms.items():
         v = np.array(v)
-        C, R, test = shape[name]
         med = float(np.median(v)) * 1e-3
-        out[name] = {"columns": C, "rows": R, "median_ms": med * 1e3, "min_ms": float(v.min()),
-                     "max_ms": float(v.max()), "spread_ms": float(v.max() - v.min()), "series_per_s": N / med,
-                     "model_bytes_per_series": model_bytes(C, R, test),
-                     "model_bytes_per_s": N * model_bytes(C, R, test) / med}
+        out[name] = {"median_ms": med * 1e3, "min_ms": float(v.min()), "max_ms": float(v.max()),
+                     "spread_ms": float(v.max() - v.min()), "series_per_s": N / med}
+        if name in shape:
+            C, R, test = shape[name]
+            out[name].update({"columns": C, "rows": R, "model_bytes_per_series": model_bytes(C, R, test),
+                              "model_bytes_per_s": N * model_bytes(C, R, test) / med})
+    for name, (_, _, n_iter) in zip(("co_shared", "co_per_series"), co):
+        it = n_iter.cpu().numpy()
+        out[name].update({"columns": 1 + k, "rows": T, "max_iter": 10, "mean_n_iter": float(it.mean()),
+                          "n_iter_histogram": {str(c): int(n) for c, n in zip(*np.unique(it, return_counts=True))}})
     for name, s in zip(calls, st):
         s = s.cpu().numpy()
         out[name]["status_counts"] = {str(c): int(n) for c, n in zip(*np.unique(s, return_counts=True))}
