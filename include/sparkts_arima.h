@@ -117,6 +117,10 @@ typedef struct arima_fit_stats {
     int64_t diag_refill_cycles;
     int64_t merge_series;        /* series the drain merge moved between bulk waves (option "merge_live")    */
     int64_t merge_waves;         /* bulk waves that handed their last series over and left                   */
+    int64_t skipped_g;           /* gradient evaluations counted in n_grad that ran no pass: after a line search whose
+                                    result the next iteration's test stops on, nothing reads the gradient. For css-cgd
+                                    fits whose points stay finite: g_passes - ride_passes + express_g_passes + skipped_g
+                                    == n_grad */
 } arima_fit_stats;
 
 /* ---- lifecycle ------------------------------------------------------------------------------------- */

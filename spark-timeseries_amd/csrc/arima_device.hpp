@@ -1039,6 +1039,7 @@ __host__ __device__ inline int ar_shape_status(int n, int p, int I) {
 __device__ __forceinline__ void fit_prep(const FitPrep &fp) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    static_assert(kFitCtlWords <= 64, "the smallest preparing launch is one wave");
     if (fp.ctl && g < kFitCtlWords) {
         unsigned long long v = 0;
         if (g == 15) v = ~0ull;                  // atomicMin of the kernel's start stamp (timing builds)
@@ -1054,6 +1055,7 @@ __device__ __forceinline__ void fit_prep(const FitPrep &fp) {
 
 // the runtime-order path's optimizer lane (arima_generic.hip): kGenMaxK padded coordinates, the first kdim real
 using GenLane = CGLane<kGenMaxK, 0, 0, true, RuntimeDim>;
+static_assert(sizeof(GenLane) == 8 + 8 * lane_doubles<kGenMaxK, 0, 0>() + 24, "the lane's size (cg_lane.hpp), after kdim");
 
 // ---- runtime-order helpers (arima_generic.hip; css-bobyqa at orders above the compiled ones) -------------------
 // a differenced row: element i = raw[i + 1] - raw[i] (dd = 1, fused differencing) or y[i] (dd = 0)

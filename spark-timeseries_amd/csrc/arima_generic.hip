@@ -254,7 +254,8 @@ __global__ __launch_bounds__(64) void k_gen_ar_fit(const double *__restrict__ y,
 
 // fitWithCSSCGD per lane: the state machine posts objective (F) or gradient (G) requests; the lane serves each with
 // one pass over its own row. Counters for arima_get_last_stats go to the fit-kernel words the runtime reads (ctl[1]
-// F passes, ctl[2] G passes, ctl[5] evaluations, ctl[6] gradients, ctl[32] series written).
+// F passes, ctl[2] G passes, ctl[5] evaluations, ctl[6] gradients, ctl[32] series written, ctl[kFitCtlSkippedG]
+// gradients counted without a pass).
 __global__ __launch_bounds__(64) void k_gen_fit(const double *__restrict__ y, int64_t ld, int n, int64_t N, int p,
                                                 int q, int I, int smear, const double *__restrict__ init,
                                                 const int32_t *__restrict__ init_status, double *__restrict__ coef_out,
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(64) void k_gen_fit(const double *__restrict__ y, in
                                                 uint8_t *__restrict__ flags_out, unsigned long long *__restrict__ ctl,
                                                 int dd) {
     const int K = I + p + q;
-    unsigned long long nf = 0, ng = 0, ne = 0, ngr = 0, done = 0;
+    unsigned long long nf = 0, ng = 0, ne = 0, ngr = 0, done = 0, skips = 0;
     for (int64_t sid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; sid < N;
          sid += (int64_t)gridDim.x * blockDim.x) {
         const int st0 = init_status ? init_status[sid] : ARIMA_ST_OK;
@@ -312,6 +313,7 @@ __global__ __launch_bounds__(64) void k_gen_fit(const double *__restrict__ y, in
         if (flags_out) flags_out[sid] = ok ? gen_model_flags(L.point, p, q, I) : 0;
         ne += L.n_eval;
         ngr += L.n_grad;
+        skips += L.skipped_g;
         ++done;
     }
     if (ctl) {
@@ -319,6 +321,7 @@ __global__ __launch_bounds__(64) void k_gen_fit(const double *__restrict__ y, in
         atomicAdd(&ctl[2], ng);
         atomicAdd(&ctl[5], ne);
         atomicAdd(&ctl[6], ngr);
+        atomicAdd(&ctl[kFitCtlSkippedG], skips);
         atomicAdd(&ctl[32], done);
     }
 }

@@ -205,6 +205,7 @@ constexpr int fit_slots_per_wave() {
     constexpr int cap = fit > 128 ? 128 : fit;
     return (cap / 8) * 8;
 }
+static_assert(kFitWavesPerCU != 4 || fit_slots_per_wave<5>() == 104, "C2's slots per wave (the lane's state must not grow)");
 
 // ---- express path: one long-running series per wave, its row in LDS -------------------------------------
 // The launch's critical path is its slowest series (a few hundred of 1M series need 10-60x the median number of
@@ -361,7 +362,7 @@ __device__ void fit_express(unsigned char *lds, int lds_bytes, const double *__r
     double *row = reinterpret_cast<double *>(gbase + express_state_bytes<K>());
     double *xch = row + ((n + 1) & ~1);                     // K + NS + 1 doubles
     unsigned long long served = 0, pf = 0, pg = 0, evals = 0, grads = 0, hits = 0, done = 0, pf_pit = 0, pg_pit = 0,
-                       pit_sw = 0;
+                       pit_sw = 0, skips = 0;
     // group state: 0 = waiting on ticket, 1 = fitting, 2 = retired (wave-uniform per group after each shfl)
     int gstate = 0;
     unsigned long long ticket = 0;
@@ -562,6 +563,7 @@ __device__ void fit_express(unsigned char *lds, int lds_bytes, const double *__r
             evals += ES.s.n_eval;
             grads += ES.s.n_grad;
             hits += ES.s.spec_hits;
+            skips += ES.s.skipped_g;
             done++;
             ticket = add_agent(&ctl[20], 1ull);
             tk_time = __builtin_amdgcn_s_memrealtime();
@@ -576,6 +578,7 @@ __device__ void fit_express(unsigned char *lds, int lds_bytes, const double *__r
         atomicAdd(&ctl[5], evals);
         atomicAdd(&ctl[6], grads);
         atomicAdd(&ctl[7], hits);
+        atomicAdd(&ctl[kFitCtlSkippedG], skips);
         atomicAdd(&ctl[32], done);
         atomicAdd(&ctl[23], served);
         atomicAdd(&ctl[24], pf);
@@ -598,7 +601,8 @@ __global__ __launch_bounds__(64 * kFitWaves) __attribute__((amdgpu_waves_per_eu(
     // ctl[8] = wave F passes with speculative chains, ctl[9] = speculative chains evaluated,
     // ctl[17] = bulk waves started, ctl[18] = objective requests served by gradient passes, ctl[20] = express tickets, ctl[21] = express fills (donations),
     // ctl[22] = bulk waves finished,
-    // ctl[23] = series finished on the express path, ctl[24] / ctl[25] = express F / G passes
+    // ctl[23] = series finished on the express path, ctl[24] / ctl[25] = express F / G passes,
+    // ctl[kFitCtlSkippedG] = gradient evaluations that needed no pass (CGLane's SKIPG; bulk and express waves)
     constexpr int K = I + P + Q;
     constexpr int NS = spec_ns<K>();
     constexpr int NJ = (SPW + 63) / 64;      // slot groups: lane l owns slots l, l + 64, ...
@@ -642,7 +646,7 @@ __global__ __launch_bounds__(64 * kFitWaves) __attribute__((amdgpu_waves_per_eu(
     FitSlot<K> *ws = slots[wave];
     const unsigned long long xring = express_ring_entries(ctl);
     unsigned long long lane_f = 0, lane_g = 0, wave_f = 0, wave_g = 0, wave_m = 0, evals = 0, grads = 0, hits = 0,
-                       chains = 0, rides = 0, done = 0, wave_chains = 0, low_passes = 0;
+                       chains = 0, rides = 0, done = 0, wave_chains = 0, low_passes = 0, skips = 0;
     unsigned round_no = 0;
     bool drained = false;                  // the batch's work counter has run out (this wave saw it)
     const bool lane0 = lane == 0;
@@ -1034,6 +1038,7 @@ __global__ __launch_bounds__(64 * kFitWaves) __attribute__((amdgpu_waves_per_eu(
                 evals += L.n_eval;
                 grads += L.n_grad;
                 hits += L.spec_hits;
+                skips += L.skipped_g;
                 done++;
                 need = true;
             }
@@ -1160,6 +1165,7 @@ __global__ __launch_bounds__(64 * kFitWaves) __attribute__((amdgpu_waves_per_eu(
     atomicAdd(&ctl[5], evals);
     atomicAdd(&ctl[6], grads);
     atomicAdd(&ctl[7], hits);
+    atomicAdd(&ctl[kFitCtlSkippedG], skips);
     atomicAdd(&ctl[9], chains);
     atomicAdd(&ctl[18], rides);
     atomicAdd(&ctl[32], done);

@@ -140,7 +140,9 @@ int launch_regress_refuse(int64_t N, int32_t status, int32_t *status_out, double
 // The fit kernel's counter words (ctl) and express-ring ready words are initialised by the kernel that runs before it
 // on the same stream (k_hr_init, else k_fit_prep): ctl[] = 0 except ctl[15] = ~0 and the option words 19, 44-47;
 // xready[0 .. xready_words) = 0. ctl == nullptr / xready_words == 0: nothing to prepare.
-constexpr int kFitCtlWords = 48;
+// Words 0-47 are the block fit_stats.hpp sums and the order search accumulates word by word; kFitCtlSkippedG follows it.
+constexpr int kFitCtlSkippedG = 48;          // gradient evaluations the optimizer counted without a pass (CGLane SKIPG)
+constexpr int kFitCtlWords = 49;
 struct FitPrep {
     unsigned long long *ctl = nullptr;
     unsigned *xready = nullptr;

@@ -54,7 +54,8 @@ struct DevBuf {
 
 constexpr int kNumEvents = 5;
 using namespace sts::stats;                    // kCtlWords and the names of the fit kernel's counter words
-static_assert(kCtlWords == sts::kFitCtlWords, "fit_stats.hpp names the words the launchers prepare");
+static_assert(kCtlWordsExt == sts::kFitCtlWords && kCtlSkippedG == sts::kFitCtlSkippedG,
+              "fit_stats.hpp names the words the launchers prepare");
 using sts::FitOut;
 
 // What arima_get_last_stats needs to turn the device counters of one fit (or slice, or host chunk) into
@@ -62,7 +63,7 @@ using sts::FitOut;
 // to pinned host memory in stream order and the stats are computed when they are asked for (fit_stats.hpp).
 struct FitRecord {
     hipEvent_t ev[kNumEvents] = {};           // start, after differencing, init, fit; (slots) after the counter copy
-    unsigned long long *ctl_host = nullptr;   // pinned, kCtlWords
+    unsigned long long *ctl_host = nullptr;   // pinned, kCtlWordsExt
     FitShape ps;
     int create() {
         for (auto &e : ev)
@@ -81,7 +82,7 @@ struct FitRecord {
         hipEventElapsedTime(&i, ev[1], ev[2]);
         hipEventElapsedTime(&f, ev[2], ev[3]);
         hipEventElapsedTime(&t, ev[0], ev[3]);
-        return fit_stats(ps, ctl_host, FitTimes{d, i, f, t});
+        return with_ext_counters(fit_stats(ps, ctl_host, FitTimes{d, i, f, t}), ps, ctl_host);
     }
 };
 
@@ -93,7 +94,7 @@ struct FitWs {
     int reserve(int64_t N, int k) {
         int rc = init.ensure((size_t)N * std::max(k, 1) * sizeof(double));
         if (rc == ARIMA_OK) rc = hr_status.ensure((size_t)N * sizeof(int32_t));
-        if (rc == ARIMA_OK) rc = ctl.ensure(kCtlWords * sizeof(unsigned long long));
+        if (rc == ARIMA_OK) rc = ctl.ensure(kCtlWordsExt * sizeof(unsigned long long));
         if (rc == ARIMA_OK) rc = xring.ensure(sts::kExpressRingBytes);
         if (rc == ARIMA_OK) rc = xready.ensure(sts::kExpressReadyBytes);
         return rc;
@@ -114,7 +115,8 @@ struct SearchLane {
                 flags.as<uint8_t>()};
     }
     DevBuf best_aic, best_order, best_coef;    // this lane's best candidate per series (merged at the end)
-    DevBuf acc;                                // kCtlWords counter sums over the lane's fits + their flops (double)
+    // kCtlWords counter sums over the lane's fits + their flops (double), then the kExtWords sums of the later words
+    DevBuf acc;
 };
 
 // A device fit larger than one slice (option "fit_slice_bytes" of differenced workspace; default 0 = 60 % of the free
@@ -244,7 +246,7 @@ struct arima_handle {
     unsigned stage_next = 0;
     int64_t fit_slice_bytes = 0;   // differenced workspace of one device-fit slice (option "fit_slice_bytes"; 0: from free HBM)
     SliceSlot slot[kSliceSlots];
-    unsigned long long *slot_ctl = nullptr;     // pinned, kCtlWords per slot
+    unsigned long long *slot_ctl = nullptr;     // pinned, kCtlWordsExt per slot
     unsigned slot_seq = 0;                      // slots taken so far
     unsigned slice_first = 0, slice_n = 0;      // slots of the last sliced fit call still pending (StatsFrom::kSlices)
     arima_fit_stats slice_acc{};                // ... and the stats of its slices whose slots were already reused
@@ -265,7 +267,9 @@ struct arima_handle {
     DevBuf os_diff[kMaxD + 1];
     hipEvent_t ev_diff[kMaxD + 1] = {};
     SearchLane lanes[kMaxSearchLanes];
-    unsigned long long *search_acc_host = nullptr;   // pinned: (kCtlWords + 1) words per lane of the last search
+    // pinned: (kCtlWords + 1) words per lane of the last search, then (from lane kMaxSearchLanes's place on) the
+    // lanes' kExtWords sums of the later words
+    unsigned long long *search_acc_host = nullptr;
     // autoFit (arima_autofit_batch*): the differenced rows, the walk state, the rounds' per-order lists and results
     DevBuf af_rows, af_dsel, af_state, af_best, af_counts, af_lists, af_off, af_coef, af_ll, af_status, af_flags;
     DevBuf af_init, af_hrst, af_rlist, af_rcount;     // the round's inits and the css-bobyqa retry list
@@ -348,7 +352,10 @@ __global__ void k_fault_take(unsigned long long *__restrict__ rec) {
 // out for AR-only fits; a fit's own stats count it there, fit_stats).
 __global__ void k_search_acc(const unsigned long long *__restrict__ ctl, unsigned long long *__restrict__ acc,
                              int64_t N, int n, int p, int q, int I, int cg) {
-    if (threadIdx.x == 0) search_acc_fit(ctl, acc, N, n, p, q, I, cg);
+    if (threadIdx.x == 0) {
+        search_acc_fit(ctl, acc, N, n, p, q, I, cg);
+        search_acc_ext(ctl, acc + kCtlWords + 1);
+    }
 }
 
 // the first watchdog fault of a fit kernel (its fault words) into the handle's sticky device record
@@ -548,15 +555,15 @@ int arima_create(int device, arima_handle **out) {
         if (rc == ARIMA_OK && hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking) != hipSuccess) rc = ARIMA_E_DEVICE;
         if (rc == ARIMA_OK) rc = c.rec.create();
         if (rc == ARIMA_OK && hipEventCreateWithFlags(&c.ev_done, hipEventDisableTiming) != hipSuccess) rc = ARIMA_E_DEVICE;
-        if (rc == ARIMA_OK && hipHostMalloc((void **)&c.rec.ctl_host, kCtlWords * sizeof(unsigned long long), 0) != hipSuccess)
+        if (rc == ARIMA_OK && hipHostMalloc((void **)&c.rec.ctl_host, kCtlWordsExt * sizeof(unsigned long long), 0) != hipSuccess)
             rc = ARIMA_E_OOM;
     }
     if (rc == ARIMA_OK &&
-        hipHostMalloc((void **)&h->slot_ctl, (size_t)kSliceSlots * kCtlWords * sizeof(unsigned long long), 0) != hipSuccess)
+        hipHostMalloc((void **)&h->slot_ctl, (size_t)kSliceSlots * kCtlWordsExt * sizeof(unsigned long long), 0) != hipSuccess)
         rc = ARIMA_E_OOM;
-    for (int j = 0; j < kSliceSlots && rc == ARIMA_OK; ++j) h->slot[j].rec.ctl_host = h->slot_ctl + (size_t)j * kCtlWords;
+    for (int j = 0; j < kSliceSlots && rc == ARIMA_OK; ++j) h->slot[j].rec.ctl_host = h->slot_ctl + (size_t)j * kCtlWordsExt;
     if (rc == ARIMA_OK && hipHostMalloc((void **)&h->search_acc_host,
-                                        (size_t)kMaxSearchLanes * (kCtlWords + 1) * sizeof(unsigned long long), 0) != hipSuccess)
+                                        (size_t)kMaxSearchLanes * (kCtlWords + 1 + kExtWords) * sizeof(unsigned long long), 0) != hipSuccess)
         rc = ARIMA_E_OOM;
     if (rc == ARIMA_OK && h->dev_fault.ensure(16 * sizeof(unsigned long long)) != ARIMA_OK) rc = ARIMA_E_OOM;
     if (rc == ARIMA_OK && hipMemset(h->dev_fault.ptr, 0, 16 * sizeof(unsigned long long)) != hipSuccess) rc = ARIMA_E_DEVICE;
@@ -648,6 +655,7 @@ int arima_get_last_stats(const arima_handle *hc, arima_fit_stats *out) {
             hipEventElapsedTime(&ms, h->ev[0], h->ev[3]);
             h->stats = search_stats(h->search_acc_host, h->search_lanes_used, h->search_n * h->search_fits,
                                     h->last_grid, h->last_express, ms);
+            search_stats_ext(h->stats, h->search_acc_host + (size_t)kMaxSearchLanes * (kCtlWords + 1), h->search_lanes_used);
             h->search_lanes_used = 0;
         }
     }
@@ -992,7 +1000,7 @@ static int fit_device_locked(arima_handle *h, FitCtx &c, FitRecord &rec, int res
     HIPCHK(h, hipEventRecord(rec.ev[3], s));
     h->last_grid = ps.grid;
     h->last_express = ps.express;
-    HIPCHK(h, hipMemcpyAsync(rec.ctl_host, c.ws.ctl.ptr, kCtlWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipMemcpyAsync(rec.ctl_host, c.ws.ctl.ptr, kCtlWordsExt * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     c.fit_ctl = &rec == &c.rec;             // check_fault reads the context's own copy only
     ps.N = N;
     ps.n = n;
@@ -2032,7 +2040,7 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         if (rc == ARIMA_OK) rc = ln.best_aic.ensure((size_t)N * sizeof(double));
         if (rc == ARIMA_OK) rc = ln.best_order.ensure((size_t)N * 4 * sizeof(int32_t));
         if (rc == ARIMA_OK) rc = ln.best_coef.ensure((size_t)N * 11 * sizeof(double));
-        if (rc == ARIMA_OK) rc = ln.acc.ensure((kCtlWords + 1) * sizeof(unsigned long long));
+        if (rc == ARIMA_OK) rc = ln.acc.ensure((kCtlWords + 1 + kExtWords) * sizeof(unsigned long long));
         if (rc != ARIMA_OK) {
             if (j == 0) return set_err(h, rc, "order search workspace");
             break;                                 // fewer lanes instead of failing the call
@@ -2066,7 +2074,7 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
         HIPCHK(h, hipStreamWaitEvent(ln.stream, h->ev[0], 0));
         RCCHK(h, sts::launch_search_init(ln.best_aic.as<double>(), ln.best_order.as<int32_t>(),
                                          ln.best_coef.as<double>(), N, ln.stream), "search_init");
-        HIPCHK(h, hipMemsetAsync(ln.acc.ptr, 0, (kCtlWords + 1) * sizeof(unsigned long long), ln.stream));
+        HIPCHK(h, hipMemsetAsync(ln.acc.ptr, 0, (kCtlWords + 1 + kExtWords) * sizeof(unsigned long long), ln.stream));
     }
     const int i_lo = intercept_mode == 1 ? 1 : 0, i_hi = intercept_mode == 0 ? 0 : 1;
     struct GridPoint { int d, p, q, I; double cost; };
@@ -2147,9 +2155,13 @@ static int order_search_locked(arima_handle *h, const double *d_series, int64_t 
     }
     RCCHK(h, sts::launch_search_merge(bests, L, N, d_aic, d_order, d_coef, s), "search_merge");
     HIPCHK(h, hipEventRecord(h->ev[3], s));
-    for (int j = 0; j < L; ++j)                    // the lanes' counter sums, read by arima_get_last_stats
+    for (int j = 0; j < L; ++j) {                  // the lanes' counter sums, read by arima_get_last_stats
         HIPCHK(h, hipMemcpyAsync(h->search_acc_host + (size_t)j * (kCtlWords + 1), h->lanes[j].acc.ptr,
                                  (kCtlWords + 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(h, hipMemcpyAsync(h->search_acc_host + (size_t)kMaxSearchLanes * (kCtlWords + 1) + (size_t)j * kExtWords,
+                                 h->lanes[j].acc.as<unsigned long long>() + kCtlWords + 1,
+                                 kExtWords * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    }
     HIPCHK(h, hipEventRecord(h->ev[4], s));
     h->stats_from = StatsFrom::kSearch;
     h->search_lanes_used = L;

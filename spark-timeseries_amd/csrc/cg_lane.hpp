@@ -14,7 +14,8 @@
 //     or, on the first iteration, the objective fused into the G(x0) pass;
 //   - the bracket's f(0) = F(point) when the direction is finite; Brent's f(mid) = the bracket's f at mid;
 //   - any non-finite point: the CSS objective and gradient are NaN (every step multiplies every coefficient);
-//   - a point whose value a speculative chain of an earlier pass of the same line search already computed.
+//   - a point whose value a speculative chain of an earlier pass of the same line search already computed;
+//   - G(point) after a line search when the next top-of-iteration test is going to stop the fit (SKIPG below).
 //
 // Speculation. Many line-search points do not depend on objective values, or depend on them only through a
 // two-way branch, so an F request carries up to NS predicted alphas (predict()): BracketFinder's golden
@@ -40,8 +41,15 @@
 
 namespace sts {
 
-constexpr int kMaxEval = 10000;      // new MaxEval(10000)  ARIMA.scala:196
-constexpr int kMaxIter = 10000;      // new MaxIter(10000)  ARIMA.scala:195
+// (macros: the CPU builds of tests/sim/skipg.mk lower the limits, to stop fits on them within milliseconds)
+#ifndef STS_CG_MAX_EVAL
+#define STS_CG_MAX_EVAL 10000
+#endif
+#ifndef STS_CG_MAX_ITER
+#define STS_CG_MAX_ITER 10000
+#endif
+constexpr int kMaxEval = STS_CG_MAX_EVAL;   // new MaxEval(10000)  ARIMA.scala:196
+constexpr int kMaxIter = STS_CG_MAX_ITER;   // new MaxIter(10000)  ARIMA.scala:195
 constexpr int kBracketMax = 500;     // commons BracketFinder() = BracketFinder(growLimit 100, maxEval 500)
 
 STS_HD STS_FI long long dbits(double x) { return __builtin_bit_cast(long long, x); }
@@ -137,7 +145,13 @@ struct RuntimeDim {
 
 // NS: predicted alphas posted with one F request; NC: values cached per line search. FF: fast-forward the
 // NaN-absorbing state in closed form (PC_TOP below); false only in the CPU simulator, to check kNanIterEvals.
-template <int K, int NS_, int NC_, bool FF = true, class DimT = KDim<K>>
+// SKIPG: the dead gradient. After a line search the reference computes G at the new point and only then, at the top
+// of the next iteration, tests MaxIter, MaxEval and convergence on objective values alone (ARIMA.scala:174-200) --
+// and F(point) there is the line search's best value, known before the gradient is. When that test is going to stop
+// the fit nothing reads the gradient, so no request is posted: the evaluation is counted (n_grad, and skipped_g for
+// the kernels' pass accounting) and the machine runs on to the stop in the same call. false only in the CPU
+// simulator, which steps both machines against each other (tests/sim/skipg_sim.cpp).
+template <int K, int NS_, int NC_, bool FF = true, class DimT = KDim<K>, bool SKIPG = true>
 struct CGLane : DimT {
     static constexpr int NS = NS_;
     static constexpr int NC = NC_;
@@ -156,6 +170,7 @@ struct CGLane : DimT {
     double rq_spec[NS1];                   // predicted alphas of the posted request
     uint16_t n_eval, n_grad, iter, bcount, spec_hits;
     uint8_t pc, status, req, have_prev_obj, have_prev, sp_n, sp_next, rq_nspec;
+    uint8_t skipped_g;                     // gradients counted without a request (SKIPG); lies in the tail padding
 
     STS_HD STS_FI void start(const double (&init)[K]) {
 #pragma unroll
@@ -167,6 +182,7 @@ struct CGLane : DimT {
         req = REQ_NONE;
         sp_n = sp_next = rq_nspec = 0;
         spec_hits = 0;
+        skipped_g = 0;
     }
 
     STS_HD STS_FI void fail(int st) {
@@ -553,9 +569,19 @@ struct CGLane : DimT {
                     point[i] = point[i] + step * dir[i];
                     pfin = pfin && finite(point[i]);
                 }
-                if (!pfin) {                          // the gradient at a non-finite point is NaN: no pass
+                // SKIPG: PC_TOP's own tests, in its order, on their inputs as PC_G leaves them (it touches none), so
+                // the stop and its status are PC_TOP's. A dead gradient goes the way of the NaN one: no request, a
+                // filled-in value (finite here: dir and delta are dead after it), PC_G and PC_TOP in this call
+                bool dead = false;
+                if constexpr (SKIPG) {
+                    dead = pfin && (iter + 1 > kMaxIter || n_eval + 1 > kMaxEval ||
+                                    (have_prev_obj && value_converged(prev_obj, memo_obj, 1e-7, 1e-7)));
+                    if (dead) skipped_g++;
+                }
+                if (!pfin || dead) {                  // the gradient at a non-finite point is NaN: no pass
+                    const double fill = pfin ? 0.0 : __builtin_nan("");
 #pragma unroll
-                    for (int i = 0; i < K; ++i) grad[i] = __builtin_nan("");
+                    for (int i = 0; i < K; ++i) grad[i] = fill;
                     pc = PC_G;
                     break;
                 }
@@ -613,5 +639,17 @@ struct CGLane : DimT {
         }
     }
 };
+
+// The state's size: the doubles, then 18 bytes of counters and flags and skipped_g in what was their padding to the
+// next 8-byte word -- so the kernels' LDS slots (k_cg_fit's slots per wave) hold as many lanes as before it
+template <int K, int NS, int NC>
+constexpr int lane_doubles() { return 2 * K + 21 + 2 * (NC > 0 ? NC : 1) + (NS > 0 ? NS : 1); }
+template <int K, int NS, int NC>
+constexpr bool lane_size_kept() { return sizeof(CGLane<K, NS, NC>) == 8 * lane_doubles<K, NS, NC>() + 24; }
+static_assert(lane_size_kept<1, 2, 4>() && lane_size_kept<2, 2, 4>() && lane_size_kept<3, 2, 4>() &&
+              lane_size_kept<4, 2, 4>() && lane_size_kept<5, 2, 4>() && lane_size_kept<6, 2, 4>() &&
+              lane_size_kept<7, 2, 4>() && lane_size_kept<8, 2, 4>() && lane_size_kept<9, 2, 4>() &&
+              lane_size_kept<10, 2, 4>() && lane_size_kept<11, 2, 4>() && lane_size_kept<5, 0, 0>(),
+              "skipped_g lies in the lane's tail padding");
 
 }  // namespace sts

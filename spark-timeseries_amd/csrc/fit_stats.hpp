@@ -35,6 +35,12 @@ enum CtlWord : int {
     kCtlMergeWaves = 42,
     kCtlWords = 48
 };
+// The kernels' words after that block. The functions below take the 48-word block and the lane sums built on it
+// (tests/sim/fitstats_sim.cpp compares them, every word and every stats member, with the bodies they replaced), so a
+// later counter is carried beside it: with_ext_counters for a fit's counter copy of kCtlWordsExt words,
+// search_acc_ext for the order search's lanes, and acc_stats for sums.
+constexpr int kCtlSkippedG = kCtlWords;       // gradient evaluations counted without a pass (cg_lane.hpp SKIPG)
+constexpr int kCtlWordsExt = kCtlWords + 1;
 constexpr int kFaultWords = kCtlFaultLast - kCtlFault + 1;
 STS_HD inline bool fault_word(int i) { return i >= kCtlFault && i <= kCtlFaultLast; }
 
@@ -143,6 +149,13 @@ inline arima_fit_stats fit_stats(const FitShape &ps, const unsigned long long *c
     return st;
 }
 
+// The same from the kernels' whole counter copy (kCtlWordsExt words): the members fed by the words after the block.
+// The flops figure counts passes that ran, so a skipped gradient is in neither G nor the flops.
+inline arima_fit_stats with_ext_counters(arima_fit_stats st, const FitShape &ps, const unsigned long long *cc) {
+    if (ps.valid) st.skipped_g = (int64_t)cc[kCtlSkippedG];
+    return st;
+}
+
 // One grid point's fit into its search lane's sums acc[kCtlWords + 1] (k_search_acc): every counter word, and the
 // fit's flops (a double in the last word). cg = 0: the AR-only shortcut or a uniform status (no counters; every series
 // written). The fault words are not summed: the lane keeps the first fault any of its fits recorded.
@@ -159,6 +172,16 @@ STS_HD inline void search_acc_fit(const unsigned long long *ctl, unsigned long l
     const bool ar_only = p > 0 && q == 0;
     double *fl = reinterpret_cast<double *>(acc + kCtlWords);
     *fl = fit_flops(*fl, N, n, p, q, I, U, G, !ar_only);
+}
+
+// The words after the block, of the same fit, into the lane's ext[kCtlWordsExt - kCtlWords] sums (k_search_acc), and
+// the lanes' sums (lanes x that many words) into the search's stats
+constexpr int kExtWords = kCtlWordsExt - kCtlWords;
+STS_HD inline void search_acc_ext(const unsigned long long *ctl, unsigned long long *ext) {
+    for (int i = 0; i < kExtWords; ++i) ext[i] += ctl[kCtlWords + i];
+}
+inline void search_stats_ext(arima_fit_stats &st, const unsigned long long *lane_ext, int lanes) {
+    for (int j = 0; j < lanes; ++j) st.skipped_g += (int64_t)lane_ext[(size_t)j * kExtWords + (kCtlSkippedG - kCtlWords)];
 }
 
 // The stats of an order search from its lanes' sums (lanes x (kCtlWords + 1) words): n_fits = series x grid points,
@@ -198,6 +221,7 @@ inline void acc_stats(arima_fit_stats &a, const arima_fit_stats &s) {
     a.flops += s.flops;
     a.n_series += s.n_series;
     for (int i = 0; i < kSummedFields; ++i) a.*kCtlFields[i].member += s.*kCtlFields[i].member;
+    a.skipped_g += s.skipped_g;
     a.grid_blocks = s.grid_blocks;
     a.express_blocks = s.express_blocks;
     if (!a.fault && s.fault) {
