@@ -354,6 +354,56 @@ int arima_regarima_co_fit_batch_device(arima_handle *h, const double *d_series, 
                                        int64_t ld, const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
                                        int32_t max_iter, double *d_coef_out, double *d_rho_out,
                                        int32_t *d_n_iter_out, int32_t *d_status_out, void *stream);
+/* ---- ARIMAX.fitModel and ARIMAXModel.forecast over a batch (ARIMAX.scala:59-161, :201-256) ------------------------ *
+ * An ARIMA(p, d, q) with exogenous regressors, restated with the reference's quirks: every output is bit-identical to
+ * tests/arimax_ref.py.
+ * Coefficients: K' = arima_arimax_num_coef = 1 + p + q + nX, nX = n_xcols * xreg_max_lag + (include_original_xreg ?
+ * n_xcols : 0): (intercept slot, AR, MA, xreg). Slot 0 exists without an intercept too (it then starts at 0.0).
+ * Fit. series N x T; xreg and x_series_stride as for the arx entry points (per series n_xcols rows of T values, 0 =
+ * shared). Without user_init the start point is: AutoregressionX.fitModel, always with an intercept, of the
+ * UNDIFFERENCED series on the matrix differenced d times as one vector of n_xcols * T values (yMaxLag = p, xMaxLag =
+ * xreg_max_lag); Hannan-Rissanen(p, q) on the differenced series, whose last q values go between the AR and the xreg
+ * part. The first exception wins: the ARX status, then Hannan-Rissanen's. user_init (N x K', nullable) skips both.
+ * The optimizer is ARIMA's css-cgd over all K' coordinates: the objective and gradient read the first I + p + q of
+ * them in ARIMA's layout (without an intercept slot 0 is read as the first AR coefficient), the others are inert but
+ * count in the restart period and come back in coef_out. The handle's "smear" option governs the gradient as for ARIMA.
+ * coef_out N x K', ll_out N (logLikelihoodCSSARMA at coef_out), status_out N (ARIMA_ST_*; a failed series has NaN
+ * coef and ll and never aborts the batch), n_eval_out / n_grad_out N, nullable (the reference's counters).
+ * Forecast. ARIMAXModel.forecast(ts, xreg): xreg per series n_xcols columns of n_future values (x_series_stride 0 =
+ * shared, else at least n_xcols * n_future); coef N x K'; out N x T: the LAST T of the T + n_future fitted and
+ * forecast values (`results.drop(nFuture)`). The coefficients are read at offset 1 whatever include_intercept says,
+ * and of xreg only column n_xcols - 1 reaches the output, times coefficient p + q + n_xcols (an assignment in the
+ * reference's sum). Shapes the reference throws for are ARIMA_E_INVALID_ARG: max(p, q) == 0, T < d, and with
+ * R = max(p, q) + max(n_future - d, 0): R < xreg_max_lag, or R - xreg_max_lag > max(p, q) + T - d. Every buffer is
+ * required, xreg also when n_future == 0 (nothing is read through it then).
+ * n_xcols < 1, negative orders, lags, T or n_future and an x_series_stride in (0, one matrix) return
+ * ARIMA_E_INVALID_ARG; p or q > 20, d > 16, K' > 41 and (d + 2) T + n_future > 2^31 - 1 return
+ * ARIMA_E_UNSUPPORTED; N == 0 returns ARIMA_OK and writes nothing. Outputs that overlap an input or one another return ARIMA_E_INVALID_ARG. A slice of series of a fit needs
+ * about (K' - q + 1) (T - max(p, xreg_max_lag)) + T doubles each (and n_xcols * T more with per-series regressors) in
+ * the workspace of "regress_slice_bytes"; results never depend on the slices.                                        */
+int arima_arimax_num_coef(int32_t n_xcols, int32_t p, int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg);
+int arima_arimax_fit_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *xreg,
+                           int64_t x_series_stride, int32_t n_xcols, int32_t p, int32_t d, int32_t q,
+                           int32_t xreg_max_lag, int32_t include_original_xreg, int32_t include_intercept,
+                           const double *user_init, double *coef_out, double *ll_out, int32_t *status_out,
+                           int32_t *n_eval_out, int32_t *n_grad_out);
+int arima_arimax_forecast_batch(arima_handle *h, const double *series, int64_t n_series, int32_t T, const double *xreg,
+                                int64_t x_series_stride, int32_t n_xcols, int32_t n_future, int32_t p, int32_t d,
+                                int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg,
+                                int32_t include_intercept, const double *coef, double *out);
+/* Same, device-resident: d_series N x T (row stride ld >= T, else ARIMA_E_INVALID_ARG), d_out N x T with row stride
+ * ld_out >= T                                                                                                       */
+int arima_arimax_fit_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                  const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t p, int32_t d,
+                                  int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg,
+                                  int32_t include_intercept, const double *d_user_init, double *d_coef_out,
+                                  double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                  int32_t *d_n_grad_out, void *stream);
+int arima_arimax_forecast_batch_device(arima_handle *h, const double *d_series, int64_t n_series, int32_t T, int64_t ld,
+                                       const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
+                                       int32_t n_future, int32_t p, int32_t d, int32_t q, int32_t xreg_max_lag,
+                                       int32_t include_original_xreg, int32_t include_intercept, const double *d_coef,
+                                       double *d_out, int64_t ld_out, void *stream);
 /* ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815) for N coefficient rows, flags_out N */
 int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t n_series, int32_t p, int32_t q,
                             int32_t include_intercept, uint8_t *flags_out);

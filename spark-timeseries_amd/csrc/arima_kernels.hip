@@ -107,11 +107,21 @@ constexpr int kFcWave = FcTile::kWave;
 constexpr int kFcRing = kFcCh + kFcMaxD;                             // LDS ring columns (>= kFcCh + kFcMaxD)
 static_assert(kFcRing >= kFcCh + kFcMaxD, "output ring too small");
 
-template <int DD, int MM>
-__global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__ ts_all, int64_t ld_in,
-                                                      const double *__restrict__ coef_all, int k,
-                                                      double *__restrict__ out_all, int64_t ld_out, int64_t N,
-                                                      int T, int p, int q, int I, int nF) {
+// ARIMAXModel.forecast (ARIMAX.scala:201-256) is the same pass with AX = true (k_arimax_forecast below): the
+// coefficients are read at offset 1 whatever I says, every step adds the xreg term between the AR and the MA terms
+// (iterateARMAX, :479-541), and only the LAST T of the T + nFuture values are written (`results.drop(nFuture)`), so the
+// tail [T-d, T+nFuture) cannot be re-integrated in place: its elements go through inverseDifferencesOfOrderD's running
+// sums as they are made. x: per series kx columns of nF values (series stride xs, 0 = shared); L = xregMaxLag.
+struct FcX {
+    const double *x;
+    int64_t xs;
+    int kx, L, orig;
+};
+
+template <int DD, int MM, bool AX>
+__device__ __forceinline__ void fc_run(const double *__restrict__ ts_all, int64_t ld_in,
+                                       const double *__restrict__ coef_all, int k, double *__restrict__ out_all,
+                                       int64_t ld_out, int64_t N, int T, int p, int q, int I, int nF, const FcX &fx) {
     constexpr int d = DD;                                              // d templated: register arrays sized to it
     constexpr int kD = DD > 0 ? DD : 1;
     constexpr int kM = MM > 0 ? MM : 1;                                // max(p, q) templated as well
@@ -132,8 +142,8 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
     double phi[kM], th[kM];
 #pragma unroll
     for (int j = 0; j < MM; ++j) {
-        phi[j] = j < p ? cf[I + j] : 0.0;
-        th[j] = j < q ? cf[I + p + j] : 0.0;
+        phi[j] = j < p ? cf[(AX ? 1 : I) + j] : 0.0;
+        th[j] = j < q ? cf[(AX ? 1 : I) + p + j] : 0.0;
     }
     const double ia = I ? c0 : 0.0;
     double xr[kM], hr[kM], ma[kM];
@@ -148,9 +158,46 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
     for (int j = 0; j < DD + 2; ++j) sr[j] = 0.0;
 
     const int lim = T - d;                                             // LDS-staged output indices [0, lim)
+    const int drop = AX ? nF : 0;                                      // result index x is output x - drop
     auto put = [&](int idx, double val) {
         if (idx < lim) ring[lane][idx % kFcRing] = val;   // idx is wave-uniform
-        else if (live) out[idx] = val;
+        else if (live && idx >= drop) out[idx - drop] = val;
+    };
+    // The xreg term of iterateARMAX's step i (`maxPQ`, :511-526): predictor row i - 1 exists for i - 1 < R - L (R = M +
+    // max(nF - d, 0) rows of the differenced, zero-prefixed matrix) and ends with column kx - 1 at index i - 1 + L
+    // (includeOriginalXreg) or i - 1 (its lag L); the assignment in the row's loop leaves that product alone, times
+    // coefficients(p + q + kx). The column is differenced on the fly (diff_at: differencesOfOrderD's operations).
+    const double *xc = nullptr;
+    double xw = 0.0;
+    int xrows = 0, xshift = 0;
+    if constexpr (AX) {
+        const bool any = fx.L > 0 || fx.orig;
+        xc = fx.x + (live ? sid : N - 1) * fx.xs + (int64_t)(fx.kx - 1) * nF;
+        xrows = any ? MM + (nF > d ? nF - d : 0) - fx.L : 0;
+        xshift = fx.orig ? fx.L : 0;
+        xw = any ? cf[p + q + fx.kx] : 0.0;
+    }
+    auto ximpact = [&](int i) -> double {
+        if (i - 1 >= xrows) return 0.0;
+        const int e = i - 1 + xshift;                                  // index into [0] * M ++ diffed.drop(d)
+        const double xv = e < MM ? 0.0 : diff_at<DD>(xc, d + e - MM);
+        return xv * xw;
+    };
+    // element tj of [diag ++ forecasts] through inverseDifferencesOfOrderD (:247-251), level d first: result T - d + tj
+    double lv[kD];
+#pragma unroll
+    for (int r = 0; r < kD; ++r) lv[r] = 0.0;
+    int tj = 0;
+    auto tail = [&](double val) {
+        double w = val;
+#pragma unroll
+        for (int l = DD; l >= 1; --l) {
+            w = tj < l ? w : w + lv[l - 1];
+            lv[l - 1] = w;
+        }
+        const int idx = T - d + tj;
+        if (live && idx >= drop) out[idx - drop] = w;
+        ++tj;
     };
     // The loads are RowTile's; its store and flush are not used: output index x is final only d steps after input x,
     // so the tile sits in the ring (nothing stored for the first tile's columns before 0) and the flush lags it by d
@@ -205,6 +252,7 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
 #pragma unroll
                 for (int j = 0; j < MM; ++j)
                     if (j < p) f = f + xr[j] * phi[j];
+                if constexpr (AX) f = f + ximpact(MM + i);
 #pragma unroll
                 for (int j = 0; j < MM; ++j)
                     if (j < q) f = f + ma[j] * th[j];
@@ -233,7 +281,8 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
 #pragma unroll
                 for (int j = 0; j < DD; ++j)
                     if (j == r) dg = Mc[j];
-                put(t, dg);
+                if constexpr (AX) tail(dg);
+                else put(t, dg);
             }
         }
         __syncthreads();                                               // ring entries of every lane written
@@ -244,7 +293,8 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
 #pragma unroll
                 for (int j = 0; j < kFcCh; ++j) {
                     const int r = FcTile::row(lane, j);
-                    if (row0 + r < N) out_all[(row0 + r) * ld_out + idx] = ring[r][idx % kFcRing];
+                    if (row0 + r < N && idx >= drop)
+                        out_all[(row0 + r) * ld_out + (idx - drop)] = ring[r][idx % kFcRing];
                 }
             }
             flushed = fe;
@@ -274,6 +324,7 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
 #pragma unroll
         for (int j = 0; j < MM; ++j)
             if (j < p) f = f + fr[j] * phi[j];
+        if constexpr (AX) f = f + ximpact(MM + i);
 #pragma unroll
         for (int j = 0; j < MM; ++j)
             if (j < q) f = f + mt[j] * th[j];
@@ -285,14 +336,32 @@ __global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__
 #pragma unroll
         for (int j = MM - 1; j >= 1; --j) fr[j] = fr[j - 1];
         fr[0] = f;
-        fo[i] = f;                                                     // :728
+        if constexpr (AX) tail(f);
+        else fo[i] = f;                                                // :728
     }
-    if (d > 0) {                                                       // inverseDifferencesOfOrderD (:756-761)
+    if (d > 0 && !AX) {                                                // inverseDifferencesOfOrderD (:756-761)
         double *w = out + (T - d);
         const int L = d + nF;
         for (int lvl = d; lvl >= 1; --lvl)
             for (int j = lvl; j < L; ++j) w[j] = w[j] + w[j - 1];
     }
+}
+
+template <int DD, int MM>
+__global__ __launch_bounds__(kFcWave) void k_forecast(const double *__restrict__ ts_all, int64_t ld_in,
+                                                      const double *__restrict__ coef_all, int k,
+                                                      double *__restrict__ out_all, int64_t ld_out, int64_t N,
+                                                      int T, int p, int q, int I, int nF) {
+    fc_run<DD, MM, false>(ts_all, ld_in, coef_all, k, out_all, ld_out, N, T, p, q, I, nF, FcX{nullptr, 0, 0, 0, 0});
+}
+
+// the streaming ARIMAX forecast at the compiled orders (1 <= max(p, q) <= 5, d <= 8); coef N x k, k = K'
+template <int DD, int MM>
+__global__ __launch_bounds__(kFcWave) void k_arimax_forecast(const double *__restrict__ ts_all, int64_t ld_in,
+                                                             const double *__restrict__ coef_all, int k,
+                                                             double *__restrict__ out_all, int64_t ld_out, int64_t N,
+                                                             int T, int p, int q, int I, int nF, FcX fx) {
+    fc_run<DD, MM, true>(ts_all, ld_in, coef_all, k, out_all, ld_out, N, T, p, q, I, nF, fx);
 }
 
 // =======================================================================================================
@@ -501,6 +570,36 @@ int launch_difference(const double *in, int64_t ld_in, double *out, int64_t ld_o
     if (N == 0 || T == 0) return ARIMA_OK;
     const unsigned grid = (unsigned)(N < 65536 * 4 ? N : 65536 * 4);
     hipLaunchKernelGGL(k_difference, dim3(grid), dim3(256), 0, s, in, ld_in, out, ld_out, N, T, d, drop);
+    STS_CHECK_LAUNCH();
+    return ARIMA_OK;
+}
+
+int launch_arimax_forecast_stream(const double *ts, int64_t ld_in, const double *x, int64_t xs, int kx,
+                                  const double *coef, int Kp, double *out, int64_t ld_out, int64_t N, int T, int p,
+                                  int d, int q, int I, int L, int orig, int n_future, hipStream_t s) {
+    if (N == 0) return ARIMA_OK;
+    const int M = p > q ? p : q;
+    if (p > kFcMaxOrder || q > kFcMaxOrder || d > kFcMaxD) return ARIMA_E_UNSUPPORTED;
+    const int64_t R = (int64_t)M + (n_future > d ? n_future - d : 0);
+    // what the kernel's indices rely on: the shapes the reference accepts (tests/arimax_ref.py forecast_check)
+    if (N < 0 || M < 1 || kx < 1 || p < 0 || q < 0 || d < 0 || L < 0 || n_future < 0 || T < d || R - L < 0 ||
+        R - L > (int64_t)M + T - d || Kp != 1 + p + q + kx * L + (orig ? kx : 0) || ld_in < T || ld_out < T ||
+        (xs != 0 && xs < (int64_t)kx * n_future) || !ts || !x || !coef || !out)
+        return ARIMA_E_INVALID_ARG;
+    const dim3 grid(grid_for(N, kFcWave)), block(kFcWave);
+    const FcX fx{x, xs, kx, L, orig ? 1 : 0};
+    switch (d * (kFcMaxOrder + 1) + M) {
+#define STS_FX_CASE(D, MM)                                                                                          \
+    case D * (kFcMaxOrder + 1) + MM:                                                                                \
+        hipLaunchKernelGGL((k_arimax_forecast<D, MM>), grid, block, 0, s, ts, ld_in, coef, Kp, out, ld_out, N, T,  \
+                           p, q, I, n_future, fx);                                                                  \
+        break;
+#define STS_FX_CASES(D) STS_FX_CASE(D, 1) STS_FX_CASE(D, 2) STS_FX_CASE(D, 3) STS_FX_CASE(D, 4) STS_FX_CASE(D, 5)
+    STS_FX_CASES(0) STS_FX_CASES(1) STS_FX_CASES(2) STS_FX_CASES(3) STS_FX_CASES(4) STS_FX_CASES(5) STS_FX_CASES(6)
+    STS_FX_CASES(7) STS_FX_CASES(8)
+#undef STS_FX_CASES
+#undef STS_FX_CASE
+    }
     STS_CHECK_LAUNCH();
     return ARIMA_OK;
 }

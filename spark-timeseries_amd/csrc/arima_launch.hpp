@@ -276,4 +276,28 @@ int launch_gen_forecast(const double *ts, int64_t ld_in, const double *coef, int
 int launch_gen_effects(const double *in, int64_t ld_in, const double *coef, int k, double *out, int64_t ld_out,
                        int64_t N, int T, int p, int d, int q, int I, int add, hipStream_t s);
 
+// ---- ARIMAX (arima_arimax.hip): K' = 1 + p + q + nX coefficients, nX = k * xregMaxLag + (includeOriginalXreg ? k : 0)
+// p, q <= kGenMaxOrder and 1 <= K' <= kGenMaxK
+bool arimax_shape_ok(int p, int q, int Kp);
+// fitModel's start point: arx N x (1 + p + nX) and its status (launch_regress_qr's), hr N x max(I + p + q, 1) and its
+// status (launch_hr_init's) -> init N x K' and the merged status, the ARX status first
+int launch_arimax_splice(const double *arx, const int32_t *arx_status, const double *hr, const int32_t *hr_status,
+                         int64_t N, int p, int q, int I, int nX, double *init, int32_t *status, hipStream_t s);
+// fitWithCSSCGD over all K' coordinates of the differenced rows y (n values, row stride ld); init N x K', init_status
+// nullable (a series whose status there is not OK gets it, NaN outputs and no fit); out.flags is not written
+int launch_arimax_fit(const double *y, int64_t ld, int n, int64_t N, int p, int q, int I, int Kp, int smear,
+                      const double *init, const int32_t *init_status, const FitOut &out, hipStream_t s);
+// the streaming kernel (arima_kernels.hip): p, q <= kFastMaxOrder and d <= 8, else ARIMA_E_UNSUPPORTED; no workspace
+int launch_arimax_forecast_stream(const double *ts, int64_t ld_in, const double *x, int64_t xs, int kx,
+                                  const double *coef, int Kp, double *out, int64_t ld_out, int64_t N, int T, int p,
+                                  int d, int q, int I, int L, int orig, int n_future, hipStream_t s);
+// every other order: the reference's arrays in a workspace, as launch_gen_forecast
+int64_t arimax_forecast_ws_doubles(int T, int p, int d, int q, int n_future);
+// ARIMAXModel.forecast: x per series kx columns of n_future values (series stride xs, 0 = shared), coef N x K',
+// out N x T; ws: ws_stride >= arimax_forecast_ws_doubles doubles per series. Shapes the reference throws for are
+// ARIMA_E_INVALID_ARG
+int launch_arimax_forecast(const double *ts, int64_t ld_in, const double *x, int64_t xs, int kx, const double *coef,
+                           int Kp, double *out, int64_t ld_out, int64_t N, int T, int p, int d, int q, int I, int L,
+                           int orig, int n_future, double *ws, int64_t ws_stride, hipStream_t s);
+
 }  // namespace sts

@@ -1984,6 +1984,237 @@ int arima_regarima_co_fit_batch_device(arima_handle *h, const double *d_series, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// ARIMAX.fitModel and ARIMAXModel.forecast (ARIMAX.scala:59-161, :201-256; arima_arimax.hip)
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct AxShape {
+    int32_t T, k, p, d, q, L, orig, I;
+    int64_t num_x() const { return (int64_t)k * L + (orig ? k : 0); }
+    int64_t num_coef() const { return 1 + (int64_t)p + q + num_x(); }
+};
+
+// argument rules shared by the ARIMAX entry points; x_rows: the rows of a regressor matrix (T for a fit, n_future for
+// a forecast); *done: nothing to compute (ARIMA_OK)
+int arimax_check(arima_handle *h, const AxShape &a, int64_t N, int64_t ld, int64_t xs, int64_t x_rows, bool *done) {
+    *done = false;
+    if (N < 0 || a.T < 0 || ld < a.T || x_rows < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (a.k < 1) return set_err(h, ARIMA_E_INVALID_ARG, "n_xcols < 1");
+    if (a.p < 0 || a.d < 0 || a.q < 0 || a.L < 0) return set_err(h, ARIMA_E_INVALID_ARG, "negative order or lag");
+    if (xs != 0 && xs < (int64_t)a.k * x_rows) return set_err(h, ARIMA_E_INVALID_ARG, "x_series_stride below one matrix");
+    if (!sts::gen_orders_ok(a.p, a.q)) return set_err(h, ARIMA_E_UNSUPPORTED, "p, q <= 20");
+    if (a.d > 16) return set_err(h, ARIMA_E_UNSUPPORTED, "d <= 16");
+    if (a.num_coef() > sts::kGenMaxK) return set_err(h, ARIMA_E_UNSUPPORTED, "at most 41 coefficients");
+    if ((int64_t)a.k * x_rows > INT32_MAX) return set_err(h, ARIMA_E_UNSUPPORTED, "regressor matrix too large");
+    // the kernels index a series' arrays of up to (d + 1) T + n_future values with int
+    if (((int64_t)a.d + 2) * a.T + x_rows > INT32_MAX) return set_err(h, ARIMA_E_UNSUPPORTED, "series too long");
+    *done = N == 0;
+    return ARIMA_OK;
+}
+
+int64_t arimax_x_doubles(const AxShape &a, int64_t N, int64_t xs, int64_t x_rows) {
+    const int64_t one = (int64_t)a.k * x_rows;
+    return one == 0 ? 0 : (xs == 0 ? one : (N - 1) * xs + one);
+}
+
+// The fit of every series, slice by slice, in the handle's regress workspace. A slice of n series holds, per series:
+// the ARX design ((C + 1) R doubles), the flat-differenced regressors (k T; one copy for the whole call when the matrix
+// is shared), the differenced series, the ARX and Hannan-Rissanen results and the start point. With user_init only the
+// differenced series is needed.
+int arimax_fit_dev(arima_handle *h, const AxShape &a, const double *y, int64_t ld, const double *x, int64_t xs, int64_t N,
+                   const double *user_init, const sts::FitOut &o, hipStream_t s) {
+    const int T = a.T, k = a.k, p = a.p, d = a.d, q = a.q, I = a.I;
+    const int nX = (int)a.num_x(), Kp = (int)a.num_coef(), Ka = 1 + p + nX, Kh = std::max(I + p + q, 1);
+    const int n = std::max(T - d, 0);
+    const int64_t ldn = row_stride(h, n), kT = (int64_t)k * T;
+    // the ARX regression always has an intercept (AutoregressionX.fitModel's default)
+    const RgDesign dsg = arx_design(T, k, p, a.L, a.orig, 0);
+    const int32_t shape = regress_shape_status(dsg);
+    const bool start = user_init == nullptr, design = start && shape == ARIMA_ST_OK;
+    const int R = design ? dsg.rows() : 0, C = design ? dsg.cols() : 0;
+    const int64_t per_series = (design ? (int64_t)(C + 1) * R + (xs ? kT : 0) : 0) + ldn +
+                               (start ? (int64_t)Ka + Kh + Kp + 2 : 0);
+    int64_t slice_bytes = h->regress_slice_bytes;
+    if (slice_bytes <= 0) {
+        size_t free_b = 0, total_b = 0;
+        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
+    }
+    const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, per_series), ns = std::min(slice, N);
+    // (the differenced rows behind them stay 128-byte aligned)
+    const int64_t ws_d = design ? sts::rg_ws_doubles(ns, R, C) : 0, dx_d = design ? round_up(xs ? ns * kT : kT, 16) : 0;
+    const int64_t start_d = start ? ns * ((int64_t)Ka + Kh + Kp + 2) : 0;
+    RCCHK(h, h->rg_ws.ensure((size_t)(ws_d + dx_d + ns * ldn + start_d + 16) * sizeof(double)), "regression workspace");
+    double *ws = h->rg_ws.as<double>(), *dx = ws + ws_d, *dy = dx + dx_d, *arx = dy + ns * ldn, *hr = arx + ns * Ka,
+           *init = hr + ns * Kh;
+    int32_t *arx_st = reinterpret_cast<int32_t *>(init + ns * Kp), *hr_st = arx_st + ns, *init_st = hr_st + ns;
+    // estimateARXCoefficients (:98-102): the column-major matrix differenced as ONE vector of k T values
+    if (design && xs == 0) RCCHK(h, sts::launch_difference(x, kT, dx, kT, 1, (int)kT, d, 0, s), "xreg difference");
+    for (int64_t f = 0; f < N; f += slice) {
+        const int64_t m = std::min(slice, N - f);
+        RCCHK(h, sts::launch_difference(y + f * ld, ld, dy, ldn, m, T, d, 1, s), "difference");
+        if (start) {
+            if (design) {
+                if (xs != 0) RCCHK(h, sts::launch_difference(x + f * xs, xs, dx, kT, m, (int)kT, d, 0, s), "xreg difference");
+                const RgSrc src{y + f * ld, ld, dx, xs ? kT : 0};
+                RCCHK(h, sts::launch_regress_assemble(dsg, src, m, ws, s), "design");
+                RCCHK(h, sts::launch_regress_qr(ws, m, R, C, arx, Ka, 0, 0, arx_st, s), "qr");
+            } else {
+                RCCHK(h, sts::launch_regress_refuse(m, shape, arx_st, arx, Ka, nullptr, 0, s), "regression");
+            }
+            // estimateMACoefficients (:111-117): the regression runs, and can throw, with q == 0 too
+            RCCHK(h, sts::launch_hr_init(dy, ldn, n, m, p, q, I, hr, hr_st, s, std::max(h->hr_grid, 0)), "hr_init");
+            RCCHK(h, sts::launch_arimax_splice(arx, arx_st, hr, hr_st, m, p, q, I, nX, init, init_st, s), "start point");
+        }
+        RCCHK(h, sts::launch_arimax_fit(dy, ldn, n, m, p, q, I, Kp, h->smear, start ? init : user_init + f * Kp,
+                                        start ? init_st : nullptr, o.at(f, Kp), s), "arimax fit");
+    }
+    return ARIMA_OK;
+}
+
+// ARIMAXModel.forecast's own shapes: the reference throws for every series alike (tests/arimax_ref.py forecast_check)
+int arimax_forecast_check(arima_handle *h, const AxShape &a, int32_t n_future) {
+    const int64_t M = std::max(a.p, a.q), R = M + std::max(n_future - a.d, 0);
+    if (M == 0) return set_err(h, ARIMA_E_INVALID_ARG, "max(p, q) == 0");
+    if (a.T < a.d) return set_err(h, ARIMA_E_INVALID_ARG, "T < d");
+    if (R - a.L < 0) return set_err(h, ARIMA_E_INVALID_ARG, "fewer differenced xreg rows than xreg_max_lag");
+    if (R - a.L > M + a.T - a.d) return set_err(h, ARIMA_E_INVALID_ARG, "more predictor rows than history");
+    return ARIMA_OK;
+}
+
+int arimax_forecast_dev(arima_handle *h, const AxShape &a, const double *ts, int64_t ld, const double *x, int64_t xs,
+                        int32_t n_future, const double *coef, double *out, int64_t ld_out, int64_t N, hipStream_t s) {
+    const int Kp = (int)a.num_coef();
+    // the streaming row-tile kernel at the compiled forecast's orders, the workspace kernel above them
+    if (!sts::gen_order(a.p, a.q) && a.d <= 8)
+        return sts::launch_arimax_forecast_stream(ts, ld, x, xs, a.k, coef, Kp, out, ld_out, N, a.T, a.p, a.d, a.q, a.I,
+                                                  a.L, a.orig, n_future, s);
+    const int64_t w = sts::arimax_forecast_ws_doubles(a.T, a.p, a.d, a.q, n_future);
+    // slices of at most 1 GiB of workspace, at least one series
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t(1) << 27) / std::max<int64_t>(w, 1)));
+    RCCHK(h, h->fc_ws.ensure((size_t)std::min(chunk, N) * w * sizeof(double)), "forecast workspace");
+    for (int64_t f = 0; f < N; f += chunk) {
+        const int64_t m = std::min(chunk, N - f);
+        RCCHK(h, sts::launch_arimax_forecast(ts + f * ld, ld, x + f * xs, xs, a.k, coef + f * Kp, Kp, out + f * ld_out,
+                                             ld_out, m, a.T, a.p, a.d, a.q, a.I, a.L, a.orig, n_future,
+                                             h->fc_ws.as<double>(), w, s), "arimax forecast");
+    }
+    return ARIMA_OK;
+}
+}  // namespace
+
+int arima_arimax_num_coef(int32_t n_xcols, int32_t p, int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg) {
+    if (n_xcols < 0 || p < 0 || q < 0 || xreg_max_lag < 0) return ARIMA_E_INVALID_ARG;
+    const int64_t K = AxShape{0, n_xcols, p, 0, q, xreg_max_lag, include_original_xreg ? 1 : 0, 1}.num_coef();
+    return K > INT32_MAX ? ARIMA_E_INVALID_ARG : (int)K;
+}
+
+int arima_arimax_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
+                           int64_t x_series_stride, int32_t n_xcols, int32_t p, int32_t d, int32_t q,
+                           int32_t xreg_max_lag, int32_t include_original_xreg, int32_t include_intercept,
+                           const double *user_init, double *coef_out, double *ll_out, int32_t *status_out,
+                           int32_t *n_eval_out, int32_t *n_grad_out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kHostBuffers);
+    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
+    bool done;
+    PASSCHK(arimax_check(h, a, N, T, x_series_stride, T, &done));
+    if (done) return ARIMA_OK;
+    if ((T > 0 && (!series || !xreg)) || !coef_out || !ll_out || !status_out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t nd = (size_t)N * sizeof(double), ni = (size_t)N * sizeof(int32_t), row_bytes = nd * T,
+                 x_bytes = (size_t)arimax_x_doubles(a, N, x_series_stride, T) * sizeof(double),
+                 coef_bytes = nd * (size_t)a.num_coef(), ui_bytes = user_init ? coef_bytes : 0;
+    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(user_init, ui_bytes)},
+                          {ByteSpan(coef_out, coef_bytes), ByteSpan(ll_out, nd), ByteSpan(status_out, ni),
+                           ByteSpan(n_eval_out, n_eval_out ? ni : 0), ByteSpan(n_grad_out, n_grad_out ? ni : 0)}));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(user_init, ui_bytes),
+                     stage_out(coef_out, coef_bytes), stage_out(ll_out, nd), stage_out(status_out, ni),
+                     stage_optional_out(n_eval_out, ni), stage_optional_out(n_grad_out, ni)}));
+    const sts::FitOut o{f.dev<double>(3), f.dev<double>(4), f.dev<int32_t>(5), f.dev<int32_t>(6), f.dev<int32_t>(7),
+                        nullptr};
+    PASSCHK(arimax_fit_dev(h, a, f.dev<double>(0), T, f.dev<double>(1), x_series_stride, N,
+                           user_init ? f.dev<double>(2) : nullptr, o, f.s()));
+    return f.finish();
+}
+
+int arima_arimax_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                  const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t p, int32_t d,
+                                  int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg,
+                                  int32_t include_intercept, const double *d_user_init, double *d_coef_out,
+                                  double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
+                                  int32_t *d_n_grad_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kDeviceBuffers);
+    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
+    bool done;
+    PASSCHK(arimax_check(h, a, N, ld, x_series_stride, T, &done));
+    if (done) return ARIMA_OK;
+    if ((T > 0 && (!d_series || !d_xreg)) || !d_coef_out || !d_ll_out || !d_status_out)
+        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int64_t sd = (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t), coef_bytes = N * a.num_coef() * sd;
+    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
+                              ByteSpan(d_xreg, arimax_x_doubles(a, N, x_series_stride, T) * sd),
+                              ByteSpan(d_user_init, d_user_init ? coef_bytes : 0)},
+                          {ByteSpan(d_coef_out, coef_bytes), ByteSpan(d_ll_out, N * sd), ByteSpan(d_status_out, ni),
+                           ByteSpan(d_n_eval_out, d_n_eval_out ? ni : 0),
+                           ByteSpan(d_n_grad_out, d_n_grad_out ? ni : 0)}));
+    PASSCHK(f.begin(stream));
+    const sts::FitOut o{d_coef_out, d_ll_out, d_status_out, d_n_eval_out, d_n_grad_out, nullptr};
+    PASSCHK(arimax_fit_dev(h, a, d_series, ld, d_xreg, x_series_stride, N, d_user_init, o, f.s()));
+    return f.finish();
+}
+
+int arima_arimax_forecast_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
+                                int64_t x_series_stride, int32_t n_xcols, int32_t n_future, int32_t p, int32_t d,
+                                int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg,
+                                int32_t include_intercept, const double *coef, double *out) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kHostBuffers);
+    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
+    bool done;
+    PASSCHK(arimax_check(h, a, N, T, x_series_stride, n_future, &done));
+    PASSCHK(arimax_forecast_check(h, a, n_future));
+    if (done || T == 0) return ARIMA_OK;
+    if (!series || !xreg || !coef || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
+                 x_bytes = (size_t)arimax_x_doubles(a, N, x_series_stride, n_future) * sizeof(double),
+                 coef_bytes = nd * (size_t)a.num_coef();
+    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(coef, coef_bytes)},
+                          {ByteSpan(out, row_bytes)}));
+    PASSCHK(f.begin());
+    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(coef, coef_bytes),
+                     stage_out(out, row_bytes)}));
+    PASSCHK(arimax_forecast_dev(h, a, f.dev<double>(0), T, f.dev<double>(1), x_series_stride, n_future,
+                                f.dev<double>(2), f.dev<double>(3), T, N, f.s()));
+    return f.finish();
+}
+
+int arima_arimax_forecast_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
+                                       const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
+                                       int32_t n_future, int32_t p, int32_t d, int32_t q, int32_t xreg_max_lag,
+                                       int32_t include_original_xreg, int32_t include_intercept, const double *d_coef,
+                                       double *d_out, int64_t ld_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, kDeviceBuffers);
+    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
+    bool done;
+    PASSCHK(arimax_check(h, a, N, ld, x_series_stride, n_future, &done));
+    if (ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    PASSCHK(arimax_forecast_check(h, a, n_future));
+    if (done || T == 0) return ARIMA_OK;
+    if (!d_series || !d_xreg || !d_coef || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
+    const int64_t sd = (int64_t)sizeof(double);
+    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
+                              ByteSpan(d_xreg, arimax_x_doubles(a, N, x_series_stride, n_future) * sd),
+                              ByteSpan(d_coef, N * a.num_coef() * sd)},
+                          {ByteSpan(d_out, ((N - 1) * ld_out + T) * sd)}));
+    PASSCHK(f.begin(stream));
+    PASSCHK(arimax_forecast_dev(h, a, d_series, ld, d_xreg, x_series_stride, n_future, d_coef, d_out, ld_out, N, f.s()));
+    return f.finish();
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // order search over (d, p, q, intercept) — SURVEY.md 8(f) row 2 (config C5)
 // ---------------------------------------------------------------------------------------------------------
 // Stream s waits for everything the first L search lanes have been given so far. The entry points join every lane,

@@ -70,6 +70,8 @@ EXPORTED = [
     "arima_arx_num_coef", "arima_arx_fit_batch", "arima_arx_fit_batch_device", "arima_arx_predict_batch",
     "arima_arx_predict_batch_device", "arima_bgtest_batch", "arima_bgtest_batch_device", "arima_bptest_batch",
     "arima_bptest_batch_device", "arima_regarima_co_fit_batch", "arima_regarima_co_fit_batch_device",
+    "arima_arimax_num_coef", "arima_arimax_fit_batch", "arima_arimax_fit_batch_device", "arima_arimax_forecast_batch",
+    "arima_arimax_forecast_batch_device",
 ]
 
 # the small models (EWMA.scala, GARCH.scala): parameters per series; ARGARCH's are (c, phi, omega, alpha, beta)
@@ -221,6 +223,15 @@ def load():
         L.arima_regarima_co_fit_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _dp, _dp, _i32p, _i32p]
         L.arima_regarima_co_fit_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _vp, _vp,
                                                          _vp, _vp, _vp]
+        L.arima_arimax_num_coef.argtypes = [_i32, _i32, _i32, _i32, _i32]
+        L.arima_arimax_fit_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                             _dp, _dp, _dp, _i32p, _i32p, _i32p]
+        L.arima_arimax_fit_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32,
+                                                    _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]
+        L.arima_arimax_forecast_batch.argtypes = [H, _dp, _i64, _i32, _dp, _i64, _i32, _i32, _i32, _i32, _i32, _i32,
+                                                  _i32, _i32, _dp, _dp]
+        L.arima_arimax_forecast_batch_device.argtypes = [H, _vp, _i64, _i32, _i64, _vp, _i64, _i32, _i32, _i32, _i32,
+                                                         _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]
         _lib = L
         return L
 
@@ -792,6 +803,81 @@ class Engine:
                                                               x_series_stride, n_xcols, int(max_iter), d_coef, d_rho,
                                                               d_n_iter, d_status, stream),
                     "arima_regarima_co_fit_batch_device")
+        if blocking:
+            self.synchronize()
+
+    # ---- ARIMAX.fitModel / ARIMAXModel.forecast over a batch (ARIMAX.scala) ----------------------------------
+    def arimax_num_coef(self, n_xcols, p, q, xreg_max_lag, include_original_xreg=True):
+        K = self.L.arima_arimax_num_coef(n_xcols, p, q, xreg_max_lag, int(bool(include_original_xreg)))
+        if K < 0:
+            raise EngineError("arima_arimax_num_coef: negative order, lag or column count")
+        return K
+
+    def arimax_fit(self, series, x, p, d, q, xreg_max_lag, include_original_xreg=True, include_intercept=True,
+                   user_init=None):
+        """ARIMAX.fitModel of every row (ARIMAX.scala:59-87); x (T, k) shared or (N, T, k); user_init (K',) or
+        (N, K'): dict(coef N x K', ll, status, n_eval, n_grad)."""
+        series = self._rows(series)
+        N, T = series.shape
+        xr, xs, k = self._xreg(x, N, T)
+        K = self.arimax_num_coef(k, p, q, xreg_max_lag, include_original_xreg)
+        ui = None
+        if user_init is not None:
+            ui = np.ascontiguousarray(np.broadcast_to(np.asarray(user_init, dtype=np.float64).reshape(-1, K), (N, K)))
+        r = dict(coef=np.empty((N, K)), ll=np.empty(N), status=np.empty(N, dtype=np.int32),
+                 n_eval=np.empty(N, dtype=np.int32), n_grad=np.empty(N, dtype=np.int32))
+        self._check(self.L.arima_arimax_fit_batch(self.h, _ptr(series), N, T, _ptr(xr), xs, k, p, d, q, xreg_max_lag,
+                                                  int(bool(include_original_xreg)), int(bool(include_intercept)),
+                                                  _ptr(ui), _ptr(r["coef"]), _ptr(r["ll"]), _ptr(r["status"], _i32p),
+                                                  _ptr(r["n_eval"], _i32p), _ptr(r["n_grad"], _i32p)),
+                    "arima_arimax_fit_batch")
+        return r
+
+    def arimax_forecast(self, series, x, p, d, q, xreg_max_lag, include_original_xreg, include_intercept, coef):
+        """ARIMAXModel.forecast of every row (:201-256); x (nFuture, k) shared or (N, nFuture, k); coef (K',) or
+        (N, K'): (N, T), the last T of the T + nFuture values."""
+        series = self._rows(series)
+        N, T = series.shape
+        x = np.asarray(x, dtype=np.float64)
+        if x.ndim not in (2, 3) or (x.ndim == 3 and x.shape[0] != N):
+            raise ValueError(f"x must be (nFuture, k) or (N, nFuture, k) with N = {N}; got {x.shape}")
+        n_future, k = x.shape[-2], x.shape[-1]
+        xr = np.ascontiguousarray(np.swapaxes(x, -1, -2))
+        xs = 0 if x.ndim == 2 else k * n_future
+        K = self.arimax_num_coef(k, p, q, xreg_max_lag, include_original_xreg)
+        coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef, dtype=np.float64).reshape(-1, K), (N, K)))
+        out = np.empty((N, T))
+        self._check(self.L.arima_arimax_forecast_batch(self.h, _ptr(series), N, T, _ptr(xr), xs, k, n_future, p, d, q,
+                                                       xreg_max_lag, int(bool(include_original_xreg)),
+                                                       int(bool(include_intercept)), _ptr(coef), _ptr(out)),
+                    "arima_arimax_forecast_batch")
+        return out
+
+    def arimax_fit_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, p, d, q, xreg_max_lag,
+                          include_original_xreg, include_intercept, d_coef, d_ll, d_status, d_n_eval=None,
+                          d_n_grad=None, d_user_init=None, stream=None, blocking=True):
+        """Device-pointer ARIMAX fits (ints = raw HBM addresses); d_xreg per series n_xcols rows of T values,
+        x_series_stride 0 = shared; d_coef N x K'."""
+        self._check(self.L.arima_arimax_fit_batch_device(self.h, d_series, n_series, T, ld, d_xreg, x_series_stride,
+                                                         n_xcols, p, d, q, xreg_max_lag,
+                                                         int(bool(include_original_xreg)),
+                                                         int(bool(include_intercept)), d_user_init, d_coef, d_ll,
+                                                         d_status, d_n_eval, d_n_grad, stream),
+                    "arima_arimax_fit_batch_device")
+        if blocking:
+            self.synchronize()
+
+    def arimax_forecast_device(self, d_series, n_series, T, ld, d_xreg, x_series_stride, n_xcols, n_future, p, d, q,
+                               xreg_max_lag, include_original_xreg, include_intercept, d_coef, d_out, ld_out,
+                               stream=None, blocking=True):
+        """Device-pointer ARIMAXModel.forecast; d_xreg per series n_xcols rows of n_future values; d_out N x T with row
+        stride ld_out."""
+        self._check(self.L.arima_arimax_forecast_batch_device(self.h, d_series, n_series, T, ld, d_xreg,
+                                                              x_series_stride, n_xcols, n_future, p, d, q,
+                                                              xreg_max_lag, int(bool(include_original_xreg)),
+                                                              int(bool(include_intercept)), d_coef, d_out, ld_out,
+                                                              stream),
+                    "arima_arimax_forecast_batch_device")
         if blocking:
             self.synchronize()
 
