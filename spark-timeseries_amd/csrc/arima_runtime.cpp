@@ -396,20 +396,11 @@ hipError_t end_call(arima_handle *h, hipStream_t s) {
     return e;
 }
 
-// One staged array of a host-buffer call: the caller's buffer, its size, and its direction. An input (`up`) is always
-// uploaded and an output (`down`) always downloaded, whatever the pointer: the entry points that do not check their
-// buffers leave a null one to the copy, which refuses it. Only an optional output is skipped when the caller passes
-// null; its region is still there for the kernel to write.
-struct Staged {
-    const void *src;
-    void *dst;
-    size_t bytes;
-    bool up, down;
-};
-inline Staged stage_in(const void *p, size_t bytes) { return {p, nullptr, bytes, true, false}; }
-inline Staged stage_out(void *p, size_t bytes) { return {nullptr, p, bytes, false, true}; }
-inline Staged stage_optional_out(void *p, size_t bytes) { return {nullptr, p, bytes, false, p != nullptr}; }
-inline Staged stage_inout(const void *src, void *dst, size_t bytes) { return {src, dst, bytes, true, true}; }
+using sts::plan::Buf;
+using sts::plan::buf_in;
+using sts::plan::buf_opt_out;
+using sts::plan::buf_out;
+using sts::plan::strided_bytes;
 
 enum CallFlavour { kDeviceBuffers, kHostBuffers };
 
@@ -418,6 +409,11 @@ enum CallFlavour { kDeviceBuffers, kHostBuffers };
 // call. From then on every way out -- finish(), or an error return from the middle of the body -- records the call's
 // end event, so later calls wait for whatever this one enqueued, and a host-buffer call also waits for its stream, so
 // no copy into the caller's arrays is in flight when it returns. The first error keeps its code and message.
+//
+// The frame also holds the call's buffer table (sts::plan::Buf, one row per pointer argument), written down once by
+// bind(). Both flavours of an entry point share one body: for device buffers dev<T>(i) is the caller's own pointer,
+// for host buffers it is row i's copy in the handle's staging block, which begin() lays out (sts::plan::arena_layout)
+// and uploads and finish() downloads. A null buffer that may be null takes no bytes and stays null for the kernels.
 class CallFrame {
   public:
     CallFrame(arima_handle *h, CallFlavour flavour) : h_(h), lk_(h->mu), host_(flavour == kHostBuffers) {}
@@ -425,41 +421,56 @@ class CallFrame {
     CallFrame &operator=(const CallFrame &) = delete;
     ~CallFrame() { close(nullptr); }
 
+    // The call's buffers; refuses a null one that is needed.
+    int bind(std::initializer_list<Buf> table) {
+        set(table);
+        if (sts::plan::missing_buffer(buf_, n_)) return set_err(h_, ARIMA_E_INVALID_ARG, "null buffer");
+        return ARIMA_OK;
+    }
+    // The rule of every entry point that checks its buffers (sts::plan::find_overlap), with its two messages
+    int overlap() {
+        switch (sts::plan::table_overlap(buf_, n_)) {
+        case sts::plan::kOutputMeetsInput: return set_err(h_, ARIMA_E_INVALID_ARG, "an output overlaps an input");
+        case sts::plan::kOutputsMeet: return set_err(h_, ARIMA_E_INVALID_ARG, "outputs overlap");
+        default: return ARIMA_OK;
+        }
+    }
+
     int begin(void *stream = nullptr) {
         HIPCHK(h_, hipSetDevice(h_->device));
         s_ = stream ? (hipStream_t)stream : h_->stream;
         begin_call(h_, s_);
         open_ = true;
-        return ARIMA_OK;
+        return host_ && n_ ? upload() : ARIMA_OK;
     }
     hipStream_t s() const { return s_; }
 
-    // Lays the call's arrays out in the handle's staging block (sts::plan::arena_layout), grows it once and uploads
-    // the inputs. dev<T>(i) is row i's device copy.
-    int stage(std::initializer_list<Staged> rows) {
-        assert(rows.size() <= (size_t)kMaxStaged);
-        size_t bytes[kMaxStaged];
-        n_ = 0;
-        for (const Staged &r : rows) {
-            row_[n_] = r;
-            bytes[n_++] = r.bytes;
-        }
-        const size_t total = sts::plan::arena_layout(bytes, n_, off_);
-        RCCHK(h_, h_->staging.ensure(std::max<size_t>(total, 256)), "staging");
-        for (int i = 0; i < n_; ++i)
-            if (row_[i].up && row_[i].bytes)
-                HIPCHK(h_, hipMemcpyAsync(at(i), row_[i].src, row_[i].bytes, hipMemcpyHostToDevice, s_));
-        return ARIMA_OK;
+    // The building blocks, which check no buffer: their table after begin() (and after their padded upload). A null
+    // buffer reaches the copy, which refuses it.
+    int stage(std::initializer_list<Buf> table) {
+        set(table);
+        return upload();
     }
     template <class T>
-    T *dev(int i) const { return reinterpret_cast<T *>(at(i)); }
+    T *dev(int i) const {
+        const bool staged = host_ && (buf_[i].p || buf_[i].need);
+        return static_cast<T *>(staged ? h_->staging.as<char>() + off_[i] : const_cast<void *>(buf_[i].p));
+    }
+    int64_t bytes(int i) const { return buf_[i].bytes; }
+
+    // staged row i to a host array of the caller's that is not the row's own (the ARIMA effects pair)
+    int download(int i, void *dst) {
+        HIPCHK(h_, hipMemcpyAsync(dst, dev<char>(i), (size_t)buf_[i].bytes, hipMemcpyDeviceToHost, s_));
+        return ARIMA_OK;
+    }
 
     // The way out of a body that got this far: after rc == ARIMA_OK the staged outputs go back to the host; then the
     // end event and, for host buffers, the wait. Returns the first error.
     int finish(int rc = ARIMA_OK) {
-        for (int i = 0; i < n_ && rc == ARIMA_OK; ++i) {
-            if (!row_[i].down || !row_[i].bytes) continue;
-            const hipError_t e = hipMemcpyAsync(row_[i].dst, at(i), row_[i].bytes, hipMemcpyDeviceToHost, s_);
+        for (int i = 0; host_ && i < n_ && rc == ARIMA_OK; ++i) {
+            if (!buf_[i].written() || !buf_[i].bytes) continue;
+            const hipError_t e = hipMemcpyAsync(const_cast<void *>(buf_[i].p), dev<char>(i), (size_t)buf_[i].bytes,
+                                                hipMemcpyDeviceToHost, s_);
             if (e != hipSuccess) rc = set_err(h_, ARIMA_E_DEVICE, hipGetErrorString(e));
         }
         close(&rc);
@@ -467,8 +478,27 @@ class CallFrame {
     }
 
   private:
-    static constexpr int kMaxStaged = 8;
-    char *at(int i) const { return h_->staging.as<char>() + off_[i]; }
+    void set(std::initializer_list<Buf> table) {
+        assert(table.size() <= (size_t)sts::plan::kMaxBufs);
+        n_ = 0;
+        for (const Buf &b : table) {
+            buf_[n_] = b;
+            if ((!b.p && !b.need) || b.bytes < 0) buf_[n_].bytes = 0;
+            ++n_;
+        }
+    }
+    // grows the staging block once for the whole table and uploads what the call reads
+    int upload() {
+        size_t bytes[sts::plan::kMaxBufs];
+        for (int i = 0; i < n_; ++i) bytes[i] = (size_t)buf_[i].bytes;
+        const size_t total = sts::plan::arena_layout(bytes, n_, off_);
+        RCCHK(h_, h_->staging.ensure(std::max<size_t>(total, 256)), "staging");
+        for (int i = 0; i < n_; ++i)
+            if (buf_[i].read() && buf_[i].bytes)
+                HIPCHK(h_, hipMemcpyAsync(h_->staging.as<char>() + off_[i], buf_[i].p, bytes[i], hipMemcpyHostToDevice,
+                                          s_));
+        return ARIMA_OK;
+    }
     void close(int *rc) {
         if (!open_) return;
         open_ = false;
@@ -485,18 +515,9 @@ class CallFrame {
     hipStream_t s_ = nullptr;
     bool open_ = false;
     int n_ = 0;
-    Staged row_[kMaxStaged];
-    size_t off_[kMaxStaged];
+    Buf buf_[sts::plan::kMaxBufs];
+    size_t off_[sts::plan::kMaxBufs];
 };
-
-// The rule of every entry point that checks its buffers (sts::plan::find_overlap), with its two messages
-int check_overlap(arima_handle *h, std::initializer_list<ByteSpan> in, std::initializer_list<ByteSpan> out) {
-    switch (sts::plan::find_overlap(in.begin(), (int)in.size(), out.begin(), (int)out.size())) {
-    case sts::plan::kOutputMeetsInput: return set_err(h, ARIMA_E_INVALID_ARG, "an output overlaps an input");
-    case sts::plan::kOutputsMeet: return set_err(h, ARIMA_E_INVALID_ARG, "outputs overlap");
-    default: return ARIMA_OK;
-    }
-}
 
 }  // namespace
 
@@ -1273,7 +1294,7 @@ int arima_difference_batch(arima_handle *h, const double *series, int64_t N, int
     if (N == 0 || T == 0) return ARIMA_OK;
     PASSCHK(f.begin());
     const size_t bytes = (size_t)N * T * sizeof(double);
-    PASSCHK(f.stage({stage_in(series, bytes), stage_out(out, bytes)}));
+    PASSCHK(f.stage({buf_in(series, bytes), buf_out(out, bytes)}));
     RCCHK(h, sts::launch_difference(f.dev<double>(0), T, f.dev<double>(1), T, N, T, d, 0, f.s()), "difference");
     return f.finish();
 }
@@ -1285,7 +1306,7 @@ int arima_inverse_difference_batch(arima_handle *h, const double *series, int64_
     if (N == 0 || T == 0) return ARIMA_OK;
     PASSCHK(f.begin());
     const size_t bytes = (size_t)N * T * sizeof(double);
-    PASSCHK(f.stage({stage_in(series, bytes), stage_out(out, bytes)}));
+    PASSCHK(f.stage({buf_in(series, bytes), buf_out(out, bytes)}));
     RCCHK(h, sts::launch_inverse_difference(f.dev<double>(0), T, f.dev<double>(1), T, N, T, d, f.s()),
           "inverse_difference");
     return f.finish();
@@ -1314,8 +1335,8 @@ int arima_css_loglik_batch(arima_handle *h, const double *series, int64_t N, int
     const int n = std::max(T - d, 0);
     const int64_t ldn = row_stride(h, n);
     RCCHK(h, h->diff.ensure((size_t)N * ldn * sizeof(double)), "workspace");
-    PASSCHK(f.stage({stage_in(series, (size_t)N * T * sizeof(double)), stage_in(coef, (size_t)N * k * sizeof(double)),
-                     stage_out(ll_out, (size_t)N * sizeof(double))}));
+    PASSCHK(f.stage({buf_in(series, (size_t)N * T * sizeof(double)), buf_in(coef, (size_t)N * k * sizeof(double)),
+                     buf_out(ll_out, (size_t)N * sizeof(double))}));
     RCCHK(h, sts::launch_difference(f.dev<double>(0), T, h->diff.as<double>(), ldn, N, T, d, 1, f.s()), "difference");
     RCCHK(h, sts::launch_css_loglik(h->diff.as<double>(), ldn, n, N, p, q, I, f.dev<double>(1), f.dev<double>(2),
                                     f.s()), "css_loglik");
@@ -1334,7 +1355,7 @@ int arima_css_gradient_batch(arima_handle *h, const double *diffed, int64_t N, i
     int64_t ld = 0;
     RCCHK(h, upload_padded(h, diffed, N, n, &ld, f.s()), "upload");
     const size_t coef_bytes = (size_t)N * k * sizeof(double);
-    PASSCHK(f.stage({stage_in(coef, coef_bytes), stage_out(grad_out, coef_bytes)}));
+    PASSCHK(f.stage({buf_in(coef, coef_bytes), buf_out(grad_out, coef_bytes)}));
     RCCHK(h, sts::launch_css_grad(h->diff.as<double>(), ld, n, N, p, q, I, h->smear, f.dev<double>(0), f.dev<double>(1),
                                   f.s()), "css_grad");
     return f.finish();
@@ -1351,8 +1372,8 @@ int arima_hannan_rissanen_batch(arima_handle *h, const double *diffed, int64_t N
     const int k = I + p + q;
     int64_t ld = 0;
     RCCHK(h, upload_padded(h, diffed, N, n, &ld, f.s()), "upload");
-    PASSCHK(f.stage({stage_out(init_out, (size_t)N * k * sizeof(double)),
-                     stage_out(status_out, (size_t)N * sizeof(int32_t))}));
+    PASSCHK(f.stage({buf_out(init_out, (size_t)N * k * sizeof(double)),
+                     buf_out(status_out, (size_t)N * sizeof(int32_t))}));
     RCCHK(h, sts::launch_hr_init(h->diff.as<double>(), ld, n, N, p, q, I, f.dev<double>(0), f.dev<int32_t>(1), f.s(),
                                  std::max(h->hr_grid, 0)), "hr_init");
     return f.finish();
@@ -1365,7 +1386,7 @@ int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t N, int3
     RCCHK(h, check_orders(h, p, 0, q, I), "orders");
     if (N <= 0) return ARIMA_OK;
     PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(coef, (size_t)N * (I + p + q) * sizeof(double)), stage_out(flags_out, (size_t)N)}));
+    PASSCHK(f.stage({buf_in(coef, (size_t)N * (I + p + q) * sizeof(double)), buf_out(flags_out, (size_t)N)}));
     RCCHK(h, sts::launch_model_flags(f.dev<double>(0), N, p, q, I, f.dev<uint8_t>(1), f.s()), "flags");
     return f.finish();
 }
@@ -1387,39 +1408,37 @@ static int forecast_any(arima_handle *h, const double *ts, int64_t ld, const dou
     return ARIMA_OK;
 }
 
+// From here on the two flavours of an operation share one body (the ARIMA effects pair excepted): the host flavour is
+// the device flavour at dense strides, on the handle's stream, over the staged copies of its arrays (CallFrame).
+static int forecast_body(arima_handle *h, CallFlavour flavour, const double *series, int64_t N, int32_t T, int64_t ld,
+                         int32_t p, int32_t d, int32_t q, int32_t I, const double *coef, int32_t n_future, double *out,
+                         int64_t ld_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, flavour);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    if (N < 0 || T < d || n_future < 0 || ld < T || ld_out < (int64_t)T + n_future)
+        return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    if (N == 0) return ARIMA_OK;
+    const int k = I + p + q;
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, T)), buf_in(coef, N * k * (int64_t)sizeof(double)),
+                    buf_out(out, strided_bytes(N, ld_out, (int64_t)T + n_future))}));
+    PASSCHK(f.begin(stream));
+    RCCHK(h, forecast_any(h, f.dev<double>(0), ld, f.dev<double>(1), k, f.dev<double>(2), ld_out, N, T, p, d, q, I,
+                          n_future, f.s()), "forecast");
+    return f.finish();
+}
+
 int arima_forecast_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p, int32_t d,
                          int32_t q, int32_t I, const double *coef, int32_t n_future, double *out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    if (N < 0 || T < d || n_future < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    if (N == 0) return ARIMA_OK;
-    if (!series || !coef || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    PASSCHK(f.begin());
-    const int k = I + p + q;
-    const int64_t L = (int64_t)T + n_future;
-    PASSCHK(f.stage({stage_in(series, (size_t)N * T * sizeof(double)), stage_in(coef, (size_t)N * k * sizeof(double)),
-                     stage_out(out, (size_t)N * L * sizeof(double))}));
-    RCCHK(h, forecast_any(h, f.dev<double>(0), T, f.dev<double>(1), k, f.dev<double>(2), L, N, T, p, d, q, I, n_future,
-                          f.s()), "forecast");
-    return f.finish();
+    return forecast_body(h, kHostBuffers, series, N, T, T, p, d, q, I, coef, n_future, out, (int64_t)T + n_future, nullptr);
 }
 
 int arima_forecast_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                 int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef, int32_t n_future,
                                 double *d_out, int64_t ld_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    if (N < 0 || T < d || n_future < 0 || ld < T || ld_out < (int64_t)T + n_future)
-        return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    if (N == 0) return ARIMA_OK;
-    if (!d_series || !d_coef || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    PASSCHK(f.begin(stream));
-    RCCHK(h, forecast_any(h, d_series, ld, d_coef, I + p + q, d_out, ld_out, N, T, p, d, q, I, n_future, f.s()),
-          "forecast");
-    return f.finish();
+    return forecast_body(h, kDeviceBuffers, d_series, N, T, ld, p, d, q, I, d_coef, n_future, d_out, ld_out, stream);
 }
+
 
 // ARIMAModel.removeTimeDependentEffects / addTimeDependentEffects over a device batch: k_effects (p, q <= 5, d <= 8,
 // the tiled streaming kernel) or the runtime-order k_gen_effects for every other order
@@ -1438,6 +1457,8 @@ static int effects_overlap(arima_handle *h, ByteSpan in, ByteSpan coef, ByteSpan
     return ARIMA_OK;
 }
 
+// This pair keeps a body per flavour: the host flavour stages the rows once, runs in place on them and downloads them
+// into `out`, so its output has no region and no row of its own, while the device flavour has two strided buffers.
 static int effects_host(arima_handle *h, const double *in, int64_t N, int32_t T, int32_t p, int32_t d, int32_t q,
                         int32_t I, const double *coef, double *out, int add) {
     if (!h) return ARIMA_E_INVALID_ARG;
@@ -1451,11 +1472,11 @@ static int effects_host(arima_handle *h, const double *in, int64_t N, int32_t T,
     PASSCHK(effects_overlap(h, ByteSpan(in, row_bytes), ByteSpan(coef, coef_bytes), ByteSpan(out, row_bytes),
                             out == in));
     PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_inout(in, out, row_bytes), stage_in(coef, coef_bytes)}));
+    PASSCHK(f.stage({buf_in(in, row_bytes), buf_in(coef, coef_bytes)}));
     // in place on the staged rows: every wave reads a tile before it writes it
     RCCHK(h, effects_any(f.dev<double>(0), T, f.dev<double>(1), k, f.dev<double>(0), T, N, T, p, d, q, I, add, f.s()),
           "effects");
-    return f.finish();
+    return f.finish(f.download(0, out));
 }
 
 static int effects_device(arima_handle *h, const double *d_in, int64_t N, int32_t T, int64_t ld, int32_t p, int32_t d,
@@ -1523,19 +1544,15 @@ int diag_check(arima_handle *h, int64_t N, int32_t T, int32_t max_lag, const Dia
     return ARIMA_OK;
 }
 
-// the four outputs (a null one is an empty span) against the call's input ranges
-int diag_spans(arima_handle *h, int64_t N, int32_t max_lag, const DiagOut &o, ByteSpan in0, ByteSpan in1) {
-    const int64_t nd = N * (int64_t)sizeof(double);
-    return check_overlap(h, {in0, in1},
-                         {ByteSpan(o.acf, nd * max_lag), ByteSpan(o.dw, nd), ByteSpan(o.lbs, nd), ByteSpan(o.lbp, nd)});
-}
-
-// The host entry points stage the four outputs as rows first .. first + 3 of the call's table; one the caller does
-// not want takes no bytes there and stays null for the kernel.
-size_t wanted(const void *out, size_t bytes) { return out ? bytes : 0; }
-DiagOut staged_outputs(const CallFrame &f, const DiagOut &o, int first) {
-    return {o.acf ? f.dev<double>(first) : nullptr, o.dw ? f.dev<double>(first + 1) : nullptr,
-            o.lbs ? f.dev<double>(first + 2) : nullptr, o.lbp ? f.dev<double>(first + 3) : nullptr};
+// The byte budget of one slice of a sliced call's workspace: the option's value if positive, else 60 % of the free HBM
+// plus what the workspace already holds (`held`), at least 1 GiB
+int auto_slice_bytes(arima_handle *h, int64_t option, size_t held, int64_t *slice_bytes) {
+    *slice_bytes = option;
+    if (option > 0) return ARIMA_OK;
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
+    *slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + held) / 10 * 6));
+    return ARIMA_OK;
 }
 
 // removeTimeDependentEffects into a bounded workspace slice, then the diagnostics of that slice, slice by slice
@@ -1543,12 +1560,8 @@ int residual_diag_dev(arima_handle *h, const double *d_series, int64_t N, int T,
                       const double *d_coef, int max_lag, const DiagOut &o, hipStream_t s) {
     const int k = I + p + q;
     const int64_t ldw = round_up(T, 16);                      // 128-B aligned residual rows
-    int64_t slice_bytes = h->diag_slice_bytes;
-    if (slice_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->dg_resid.bytes) / 10 * 6));
-    }
+    int64_t slice_bytes;
+    PASSCHK(auto_slice_bytes(h, h->diag_slice_bytes, h->dg_resid.bytes, &slice_bytes));
     const int64_t slice = sts::plan::diag_slice_rows(slice_bytes, ldw);
     RCCHK(h, h->dg_resid.ensure((size_t)std::min(slice, N) * ldw * sizeof(double)), "residual workspace");
     double *resid = h->dg_resid.as<double>();
@@ -1563,89 +1576,72 @@ int residual_diag_dev(arima_handle *h, const double *d_series, int64_t N, int T,
 }
 }  // namespace
 
-int arima_diagnostics_batch(arima_handle *h, const double *rows, int64_t N, int32_t T, int32_t max_lag,
-                            double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
+static int diag_body(arima_handle *h, CallFlavour flavour, const double *rows, int64_t N, int32_t T, int64_t ld,
+                     int32_t max_lag, const DiagOut &o, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
+    CallFrame f(h, flavour);
+    if (ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     bool done;
     RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
     if (done) return ARIMA_OK;
-    if (!rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t row_bytes = (size_t)N * T * sizeof(double), nd = (size_t)N * sizeof(double);
-    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(rows, row_bytes), ByteSpan()), "overlap");
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(rows, row_bytes), stage_optional_out(o.acf, wanted(o.acf, nd * max_lag)),
-                     stage_optional_out(o.dw, wanted(o.dw, nd)), stage_optional_out(o.lbs, wanted(o.lbs, nd)),
-                     stage_optional_out(o.lbp, wanted(o.lbp, nd))}));
-    const DiagOut dev = staged_outputs(f, o, 1);
-    RCCHK(h, sts::launch_diag(f.dev<double>(0), T, N, T, max_lag, dev.acf, dev.dw, dev.lbs, dev.lbp, f.s()),
-          "diagnostics");
+    const int64_t nd = N * (int64_t)sizeof(double);
+    PASSCHK(f.bind({buf_in(rows, strided_bytes(N, ld, T)), buf_opt_out(o.acf, nd * max_lag), buf_opt_out(o.dw, nd),
+                    buf_opt_out(o.lbs, nd), buf_opt_out(o.lbp, nd)}));
+    RCCHK(h, f.overlap(), "overlap");
+    PASSCHK(f.begin(stream));
+    RCCHK(h, sts::launch_diag(f.dev<double>(0), ld, N, T, max_lag, f.dev<double>(1), f.dev<double>(2), f.dev<double>(3),
+                              f.dev<double>(4), f.s()), "diagnostics");
     return f.finish();
+}
+
+int arima_diagnostics_batch(arima_handle *h, const double *rows, int64_t N, int32_t T, int32_t max_lag,
+                            double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
+    return diag_body(h, kHostBuffers, rows, N, T, T, max_lag, {acf_out, dw_out, lb_stat_out, lb_pvalue_out}, nullptr);
 }
 
 int arima_diagnostics_batch_device(arima_handle *h, const double *d_rows, int64_t N, int32_t T, int64_t ld,
                                    int32_t max_lag, double *d_acf_out, double *d_dw_out, double *d_lb_stat_out,
                                    double *d_lb_pvalue_out, void *stream) {
+    return diag_body(h, kDeviceBuffers, d_rows, N, T, ld, max_lag,
+                     {d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out}, stream);
+}
+
+static int residual_diag_body(arima_handle *h, CallFlavour flavour, const double *series, int64_t N, int32_t T,
+                              int64_t ld, int32_t p, int32_t d, int32_t q, int32_t I, const double *coef,
+                              int32_t max_lag, const DiagOut &o, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
-    if (ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    CallFrame f(h, flavour);
+    RCCHK(h, check_orders(h, p, d, q, I), "orders");
+    if (T < d || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     bool done;
     RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
     if (done) return ARIMA_OK;
-    if (!d_rows) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(d_rows, ((N - 1) * ld + T) * (int64_t)sizeof(double)), ByteSpan()),
-          "overlap");
+    const int k = I + p + q;
+    const int64_t nd = N * (int64_t)sizeof(double);
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, T)), buf_in(coef, nd * k, k > 0),
+                    buf_opt_out(o.acf, nd * max_lag), buf_opt_out(o.dw, nd), buf_opt_out(o.lbs, nd),
+                    buf_opt_out(o.lbp, nd)}));
+    RCCHK(h, f.overlap(), "overlap");
     PASSCHK(f.begin(stream));
-    RCCHK(h, sts::launch_diag(d_rows, ld, N, T, max_lag, o.acf, o.dw, o.lbs, o.lbp, f.s()), "diagnostics");
+    const DiagOut dev{f.dev<double>(2), f.dev<double>(3), f.dev<double>(4), f.dev<double>(5)};
+    RCCHK(h, residual_diag_dev(h, f.dev<double>(0), N, T, ld, p, d, q, I, f.dev<double>(1), max_lag, dev, f.s()),
+          "residual diagnostics");
     return f.finish();
 }
 
 int arima_residual_diagnostics_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
                                      int32_t d, int32_t q, int32_t I, const double *coef, int32_t max_lag,
                                      double *acf_out, double *dw_out, double *lb_stat_out, double *lb_pvalue_out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    const DiagOut o{acf_out, dw_out, lb_stat_out, lb_pvalue_out};
-    if (T < d) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    bool done;
-    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
-    if (done) return ARIMA_OK;
-    const int k = I + p + q;
-    if (!series || (!coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t row_bytes = (size_t)N * T * sizeof(double), coef_bytes = (size_t)N * k * sizeof(double),
-                 nd = (size_t)N * sizeof(double);
-    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(series, row_bytes), ByteSpan(coef, coef_bytes)), "overlap");
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(coef, coef_bytes),
-                     stage_optional_out(o.acf, wanted(o.acf, nd * max_lag)), stage_optional_out(o.dw, wanted(o.dw, nd)),
-                     stage_optional_out(o.lbs, wanted(o.lbs, nd)), stage_optional_out(o.lbp, wanted(o.lbp, nd))}));
-    RCCHK(h, residual_diag_dev(h, f.dev<double>(0), N, T, T, p, d, q, I, f.dev<double>(1), max_lag,
-                               staged_outputs(f, o, 2), f.s()), "residual diagnostics");
-    return f.finish();
+    return residual_diag_body(h, kHostBuffers, series, N, T, T, p, d, q, I, coef, max_lag,
+                              {acf_out, dw_out, lb_stat_out, lb_pvalue_out}, nullptr);
 }
 
 int arima_residual_diagnostics_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                             int32_t p, int32_t d, int32_t q, int32_t I, const double *d_coef,
                                             int32_t max_lag, double *d_acf_out, double *d_dw_out,
                                             double *d_lb_stat_out, double *d_lb_pvalue_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    RCCHK(h, check_orders(h, p, d, q, I), "orders");
-    const DiagOut o{d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out};
-    if (T < d || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    bool done;
-    RCCHK(h, diag_check(h, N, T, max_lag, o, &done), "diagnostics");
-    if (done) return ARIMA_OK;
-    const int k = I + p + q;
-    if (!d_series || (!d_coef && k > 0)) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    RCCHK(h, diag_spans(h, N, max_lag, o, ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
-                        ByteSpan(d_coef, N * k * (int64_t)sizeof(double))), "overlap");
-    PASSCHK(f.begin(stream));
-    RCCHK(h, residual_diag_dev(h, d_series, N, T, ld, p, d, q, I, d_coef, max_lag, o, f.s()), "residual diagnostics");
-    return f.finish();
+    return residual_diag_body(h, kDeviceBuffers, d_series, N, T, ld, p, d, q, I, d_coef, max_lag,
+                              {d_acf_out, d_dw_out, d_lb_stat_out, d_lb_pvalue_out}, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1680,13 +1676,18 @@ int regress_check(arima_handle *h, const RgDesign &d, int64_t N, int64_t ld, int
     return ARIMA_OK;
 }
 
-// doubles of the caller's regressor block: one matrix, or N of them x_series_stride apart
-int64_t regress_x_doubles(const RgDesign &d, int64_t N, int64_t xs) {
-    const int64_t one = (int64_t)d.k * d.T;
-    return one == 0 ? 0 : (xs == 0 ? one : (N - 1) * xs + one);
+// The caller's regressor block as a table row: one matrix of x_doubles values, or N of them x_series_stride apart. A
+// block without values may be null.
+Buf x_block(const double *x, int64_t x_doubles, int64_t N, int64_t xs) {
+    const int64_t bytes = strided_bytes(xs ? N : 1, xs, x_doubles);
+    return buf_in(x, bytes, bytes > 0);
 }
 
-bool regress_null_input(const RgDesign &d, const RgSrc &src) { return d.T > 0 && (!src.y || (d.k > 0 && !src.x)); }
+// What the design kernels read, for the entry points whose table starts with the rows and the regressor block; a
+// block without values is null for them
+RgSrc rg_src(const CallFrame &f, int64_t ld, int64_t xs) {
+    return {f.dev<double>(0), ld, f.bytes(1) ? f.dev<double>(1) : nullptr, xs};
+}
 
 // The fit (coef_out: N x (1 + K)) or the test (stat_out, pvalue_out: N) of every series, slice by slice: assemble, QR
 // and, for a test, assemble again and calculateRSquared
@@ -1700,12 +1701,8 @@ int regress_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N,
                                             test ? pvalue_out : nullptr, 1, s), "regression");
         return ARIMA_OK;
     }
-    int64_t slice_bytes = h->regress_slice_bytes;
-    if (slice_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
-    }
+    int64_t slice_bytes;
+    PASSCHK(auto_slice_bytes(h, h->regress_slice_bytes, h->rg_ws.bytes, &slice_bytes));
     const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, (int64_t)(C + 1) * R);
     RCCHK(h, h->rg_ws.ensure((size_t)sts::rg_ws_doubles(std::min(slice, N), R, C) * sizeof(double)),
           "regression workspace");
@@ -1728,53 +1725,25 @@ int regress_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N,
     return ARIMA_OK;
 }
 
-int regress_host(arima_handle *h, const RgDesign &d, const double *rows, int64_t N, const double *xreg, int64_t xs,
-                 double *coef_out, double *stat_out, double *pvalue_out, int32_t *status_out) {
+// AutoregressionX.fitModel (coef_out) or a test (stat_out, pvalue_out); the pointers of the other kind are null
+int regress_body(arima_handle *h, CallFlavour flavour, const RgDesign &d, const double *rows, int64_t N, int64_t ld,
+                 const double *xreg, int64_t xs, double *coef_out, double *stat_out, double *pvalue_out,
+                 int32_t *status_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    bool done;
-    PASSCHK(regress_check(h, d, N, d.T, xs, &done));
-    if (done) return ARIMA_OK;
-    const bool test = d.kind != sts::kRgArx;
-    if (regress_null_input(d, {rows, d.T, xreg, xs}) || !status_out || (test ? !stat_out || !pvalue_out : !coef_out))
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * d.T,
-                 x_bytes = (size_t)regress_x_doubles(d, N, xs) * sizeof(double),
-                 o0 = test ? nd : nd * (1 + (size_t)d.num_pred()), o1 = test ? nd : 0,
-                 st_bytes = (size_t)N * sizeof(int32_t);
-    double *out0 = test ? stat_out : coef_out;
-    PASSCHK(check_overlap(h, {ByteSpan(rows, row_bytes), ByteSpan(xreg, x_bytes)},
-                          {ByteSpan(out0, o0), ByteSpan(pvalue_out, o1), ByteSpan(status_out, st_bytes)}));
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(rows, row_bytes), stage_in(xreg, x_bytes), stage_out(out0, o0),
-                     stage_optional_out(test ? pvalue_out : nullptr, o1), stage_out(status_out, st_bytes)}));
-    const RgSrc src{f.dev<double>(0), d.T, x_bytes ? f.dev<double>(1) : nullptr, xs};
-    PASSCHK(regress_dev(h, d, src, N, test ? nullptr : f.dev<double>(2), test ? f.dev<double>(2) : nullptr,
-                        f.dev<double>(3), f.dev<int32_t>(4), f.s()));
-    return f.finish();
-}
-
-int regress_device(arima_handle *h, const RgDesign &d, const double *d_rows, int64_t N, int64_t ld,
-                   const double *d_xreg, int64_t xs, double *coef_out, double *stat_out, double *pvalue_out,
-                   int32_t *status_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
+    CallFrame f(h, flavour);
     bool done;
     PASSCHK(regress_check(h, d, N, ld, xs, &done));
     if (done) return ARIMA_OK;
     const bool test = d.kind != sts::kRgArx;
-    const RgSrc src{d_rows, ld, (int64_t)d.k * d.T ? d_xreg : nullptr, xs};
-    if (regress_null_input(d, {d_rows, ld, d_xreg, xs}) || !status_out || (test ? !stat_out || !pvalue_out : !coef_out))
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int64_t nd = N * (int64_t)sizeof(double);
-    double *out0 = test ? stat_out : coef_out;
-    PASSCHK(check_overlap(h, {ByteSpan(d_rows, ((N - 1) * ld + d.T) * (int64_t)sizeof(double)),
-                              ByteSpan(d_xreg, regress_x_doubles(d, N, xs) * (int64_t)sizeof(double))},
-                          {ByteSpan(out0, test ? nd : nd * (1 + d.num_pred())),
-                           ByteSpan(test ? pvalue_out : nullptr, nd),
-                           ByteSpan(status_out, N * (int64_t)sizeof(int32_t))}));
+    PASSCHK(f.bind({buf_in(rows, strided_bytes(N, ld, d.T), d.T > 0), x_block(xreg, (int64_t)d.k * d.T, N, xs),
+                    test ? buf_out(stat_out, nd) : buf_out(coef_out, nd * (1 + d.num_pred())),
+                    test ? buf_out(pvalue_out, nd) : buf_opt_out(nullptr, 0),
+                    buf_out(status_out, N * (int64_t)sizeof(int32_t))}));
+    PASSCHK(f.overlap());
     PASSCHK(f.begin(stream));
-    PASSCHK(regress_dev(h, d, src, N, coef_out, stat_out, pvalue_out, status_out, f.s()));
+    PASSCHK(regress_dev(h, d, rg_src(f, ld, xs), N, test ? nullptr : f.dev<double>(2), test ? f.dev<double>(2) : nullptr,
+                        f.dev<double>(3), f.dev<int32_t>(4), f.s()));
     return f.finish();
 }
 
@@ -1800,91 +1769,78 @@ int arima_arx_num_coef(int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag, in
 int arima_arx_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
                         int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
                         int32_t include_original_x, int32_t no_intercept, double *coef_out, int32_t *status_out) {
-    return regress_host(h, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept), series, N,
-                        xreg, x_series_stride, coef_out, nullptr, nullptr, status_out);
+    return regress_body(h, kHostBuffers, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept),
+                        series, N, T, xreg, x_series_stride, coef_out, nullptr, nullptr, status_out, nullptr);
 }
 
 int arima_arx_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
                                int32_t x_max_lag, int32_t include_original_x, int32_t no_intercept, double *d_coef_out,
                                int32_t *d_status_out, void *stream) {
-    return regress_device(h, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept), d_series,
-                          N, ld, d_xreg, x_series_stride, d_coef_out, nullptr, nullptr, d_status_out, stream);
+    return regress_body(h, kDeviceBuffers,
+                        arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, no_intercept), d_series, N, ld,
+                        d_xreg, x_series_stride, d_coef_out, nullptr, nullptr, d_status_out, stream);
+}
+
+static int predict_body(arima_handle *h, CallFlavour flavour, const RgDesign &d, const double *series, int64_t N,
+                        int64_t ld, const double *xreg, int64_t xs, const double *coef, double *out, int64_t ld_out,
+                        void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, flavour);
+    bool done;
+    PASSCHK(predict_check(h, d, N, ld, xs, ld_out, &done));
+    if (done) return ARIMA_OK;
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, d.T), d.T > 0), x_block(xreg, (int64_t)d.k * d.T, N, xs),
+                    buf_in(coef, N * (1 + d.num_pred()) * (int64_t)sizeof(double)),
+                    buf_out(out, strided_bytes(N, ld_out, d.rows()))}));
+    PASSCHK(f.overlap());
+    PASSCHK(f.begin(stream));
+    RCCHK(h, sts::launch_arx_predict(d, rg_src(f, ld, xs), f.dev<double>(2), f.dev<double>(3), ld_out, N, f.s()),
+          "predict");
+    return f.finish();
 }
 
 int arima_arx_predict_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
                             int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag, int32_t x_max_lag,
                             int32_t include_original_x, const double *coef, double *out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
     const RgDesign d = arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, 1);
-    bool done;
-    PASSCHK(predict_check(h, d, N, T, x_series_stride, d.rows(), &done));
-    if (done) return ARIMA_OK;
-    if (regress_null_input(d, {series, T, xreg, x_series_stride}) || !coef || !out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
-                 x_bytes = (size_t)regress_x_doubles(d, N, x_series_stride) * sizeof(double),
-                 coef_bytes = nd * (1 + (size_t)d.num_pred()), out_bytes = nd * d.rows();
-    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(coef, coef_bytes)},
-                          {ByteSpan(out, out_bytes)}));
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(coef, coef_bytes),
-                     stage_out(out, out_bytes)}));
-    const RgSrc src{f.dev<double>(0), T, x_bytes ? f.dev<double>(1) : nullptr, x_series_stride};
-    RCCHK(h, sts::launch_arx_predict(d, src, f.dev<double>(2), f.dev<double>(3), d.rows(), N, f.s()), "predict");
-    return f.finish();
+    return predict_body(h, kHostBuffers, d, series, N, T, xreg, x_series_stride, coef, out, d.rows(), nullptr);
 }
 
 int arima_arx_predict_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                    const double *d_xreg, int64_t x_series_stride, int32_t n_xcols, int32_t y_max_lag,
                                    int32_t x_max_lag, int32_t include_original_x, const double *d_coef, double *d_out,
                                    int64_t ld_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    const RgDesign d = arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, 1);
-    bool done;
-    PASSCHK(predict_check(h, d, N, ld, x_series_stride, ld_out, &done));
-    if (done) return ARIMA_OK;
-    if (regress_null_input(d, {d_series, ld, d_xreg, x_series_stride}) || !d_coef || !d_out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int64_t sd = (int64_t)sizeof(double);
-    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
-                              ByteSpan(d_xreg, regress_x_doubles(d, N, x_series_stride) * sd),
-                              ByteSpan(d_coef, N * (1 + d.num_pred()) * sd)},
-                          {ByteSpan(d_out, ((N - 1) * ld_out + d.rows()) * sd)}));
-    PASSCHK(f.begin(stream));
-    const RgSrc src{d_series, ld, (int64_t)d.k * T ? d_xreg : nullptr, x_series_stride};
-    RCCHK(h, sts::launch_arx_predict(d, src, d_coef, d_out, ld_out, N, f.s()), "predict");
-    return f.finish();
+    return predict_body(h, kDeviceBuffers, arx_design(T, n_xcols, y_max_lag, x_max_lag, include_original_x, 1), d_series,
+                        N, ld, d_xreg, x_series_stride, d_coef, d_out, ld_out, stream);
 }
 
 int arima_bgtest_batch(arima_handle *h, const double *residuals, int64_t N, int32_t T, const double *factors,
                        int64_t x_series_stride, int32_t n_xcols, int32_t max_lag, double *stat_out, double *pvalue_out,
                        int32_t *status_out) {
-    return regress_host(h, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, residuals, N, factors, x_series_stride, nullptr,
-                        stat_out, pvalue_out, status_out);
+    return regress_body(h, kHostBuffers, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, residuals, N, T, factors,
+                        x_series_stride, nullptr, stat_out, pvalue_out, status_out, nullptr);
 }
 
 int arima_bgtest_batch_device(arima_handle *h, const double *d_residuals, int64_t N, int32_t T, int64_t ld,
                               const double *d_factors, int64_t x_series_stride, int32_t n_xcols, int32_t max_lag,
                               double *d_stat_out, double *d_pvalue_out, int32_t *d_status_out, void *stream) {
-    return regress_device(h, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, d_residuals, N, ld, d_factors, x_series_stride,
-                          nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
+    return regress_body(h, kDeviceBuffers, {sts::kRgBg, T, n_xcols, max_lag, 0, 0, 1}, d_residuals, N, ld, d_factors,
+                        x_series_stride, nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
 }
 
 int arima_bptest_batch(arima_handle *h, const double *residuals, int64_t N, int32_t T, const double *factors,
                        int64_t x_series_stride, int32_t n_xcols, double *stat_out, double *pvalue_out,
                        int32_t *status_out) {
-    return regress_host(h, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, residuals, N, factors, x_series_stride, nullptr,
-                        stat_out, pvalue_out, status_out);
+    return regress_body(h, kHostBuffers, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, residuals, N, T, factors,
+                        x_series_stride, nullptr, stat_out, pvalue_out, status_out, nullptr);
 }
 
 int arima_bptest_batch_device(arima_handle *h, const double *d_residuals, int64_t N, int32_t T, int64_t ld,
                               const double *d_factors, int64_t x_series_stride, int32_t n_xcols, double *d_stat_out,
                               double *d_pvalue_out, int32_t *d_status_out, void *stream) {
-    return regress_device(h, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, d_residuals, N, ld, d_factors, x_series_stride,
-                          nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
+    return regress_body(h, kDeviceBuffers, {sts::kRgBp, T, n_xcols, 0, 0, 0, 1}, d_residuals, N, ld, d_factors,
+                        x_series_stride, nullptr, d_stat_out, d_pvalue_out, d_status_out, stream);
 }
 
 // RegressionARIMA.fitCochraneOrcutt (RegressionARIMA.scala:83-160): regress_check's rules on the pristine-copy design,
@@ -1912,12 +1868,8 @@ int co_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N, int3
         if (n_iter_out) HIPCHK(h, hipMemsetAsync(n_iter_out, 0, (size_t)N * sizeof(int32_t), s));
         return ARIMA_OK;
     }
-    int64_t slice_bytes = h->regress_slice_bytes;
-    if (slice_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
-    }
+    int64_t slice_bytes;
+    PASSCHK(auto_slice_bytes(h, h->regress_slice_bytes, h->rg_ws.bytes, &slice_bytes));
     const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, (int64_t)(2 * k + 3) * T);
     const int64_t copy_doubles = sts::rg_ws_doubles(std::min(slice, N), T, k);
     RCCHK(h, h->rg_ws.ensure((size_t)(copy_doubles + sts::rg_ws_doubles(std::min(slice, N), T, k + 1)) *
@@ -1934,53 +1886,39 @@ int co_dev(arima_handle *h, const RgDesign &d, const RgSrc &src, int64_t N, int3
 }
 }  // namespace
 
+static int co_body(arima_handle *h, CallFlavour flavour, const double *series, int64_t N, int32_t T, int64_t ld,
+                   const double *xreg, int64_t xs, int32_t n_xcols, int32_t max_iter, double *coef_out, double *rho_out,
+                   int32_t *n_iter_out, int32_t *status_out, void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, flavour);
+    const RgDesign d{sts::kRgCo, T, n_xcols, 0, 0, 0, 0};
+    bool done;
+    PASSCHK(co_check(h, d, N, ld, xs, max_iter, &done));
+    if (done) return ARIMA_OK;
+    const int64_t nd = N * (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t);
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, T), T > 0), x_block(xreg, (int64_t)n_xcols * T, N, xs),
+                    buf_out(coef_out, nd * (1 + n_xcols)), buf_out(rho_out, nd), buf_opt_out(n_iter_out, ni),
+                    buf_out(status_out, ni)}));
+    PASSCHK(f.overlap());
+    PASSCHK(f.begin(stream));
+    PASSCHK(co_dev(h, d, rg_src(f, ld, xs), N, max_iter, f.dev<double>(2), f.dev<double>(3), f.dev<int32_t>(4),
+                   f.dev<int32_t>(5), f.s()));
+    return f.finish();
+}
+
 int arima_regarima_co_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
                                 int64_t x_series_stride, int32_t n_xcols, int32_t max_iter, double *coef_out,
                                 double *rho_out, int32_t *n_iter_out, int32_t *status_out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    const RgDesign d{sts::kRgCo, T, n_xcols, 0, 0, 0, 0};
-    bool done;
-    PASSCHK(co_check(h, d, N, T, x_series_stride, max_iter, &done));
-    if (done) return ARIMA_OK;
-    if (regress_null_input(d, {series, T, xreg, x_series_stride}) || !coef_out || !rho_out || !status_out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
-                 x_bytes = (size_t)regress_x_doubles(d, N, x_series_stride) * sizeof(double),
-                 coef_bytes = nd * (1 + (size_t)n_xcols), ni = (size_t)N * sizeof(int32_t);
-    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes)},
-                          {ByteSpan(coef_out, coef_bytes), ByteSpan(rho_out, nd),
-                           ByteSpan(n_iter_out, n_iter_out ? ni : 0), ByteSpan(status_out, ni)}));
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_out(coef_out, coef_bytes),
-                     stage_out(rho_out, nd), stage_optional_out(n_iter_out, ni), stage_out(status_out, ni)}));
-    const RgSrc src{f.dev<double>(0), T, x_bytes ? f.dev<double>(1) : nullptr, x_series_stride};
-    PASSCHK(co_dev(h, d, src, N, max_iter, f.dev<double>(2), f.dev<double>(3), f.dev<int32_t>(4), f.dev<int32_t>(5),
-                   f.s()));
-    return f.finish();
+    return co_body(h, kHostBuffers, series, N, T, T, xreg, x_series_stride, n_xcols, max_iter, coef_out, rho_out,
+                   n_iter_out, status_out, nullptr);
 }
 
 int arima_regarima_co_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                        const double *d_xreg, int64_t x_series_stride, int32_t n_xcols,
                                        int32_t max_iter, double *d_coef_out, double *d_rho_out,
                                        int32_t *d_n_iter_out, int32_t *d_status_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    const RgDesign d{sts::kRgCo, T, n_xcols, 0, 0, 0, 0};
-    bool done;
-    PASSCHK(co_check(h, d, N, ld, x_series_stride, max_iter, &done));
-    if (done) return ARIMA_OK;
-    if (regress_null_input(d, {d_series, ld, d_xreg, x_series_stride}) || !d_coef_out || !d_rho_out || !d_status_out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int64_t nd = N * (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t);
-    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
-                              ByteSpan(d_xreg, regress_x_doubles(d, N, x_series_stride) * (int64_t)sizeof(double))},
-                          {ByteSpan(d_coef_out, nd * (1 + n_xcols)), ByteSpan(d_rho_out, nd),
-                           ByteSpan(d_n_iter_out, d_n_iter_out ? ni : 0), ByteSpan(d_status_out, ni)}));
-    PASSCHK(f.begin(stream));
-    const RgSrc src{d_series, ld, (int64_t)n_xcols * T ? d_xreg : nullptr, x_series_stride};
-    PASSCHK(co_dev(h, d, src, N, max_iter, d_coef_out, d_rho_out, d_n_iter_out, d_status_out, f.s()));
-    return f.finish();
+    return co_body(h, kDeviceBuffers, d_series, N, T, ld, d_xreg, x_series_stride, n_xcols, max_iter, d_coef_out,
+                   d_rho_out, d_n_iter_out, d_status_out, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -2011,11 +1949,6 @@ int arimax_check(arima_handle *h, const AxShape &a, int64_t N, int64_t ld, int64
     return ARIMA_OK;
 }
 
-int64_t arimax_x_doubles(const AxShape &a, int64_t N, int64_t xs, int64_t x_rows) {
-    const int64_t one = (int64_t)a.k * x_rows;
-    return one == 0 ? 0 : (xs == 0 ? one : (N - 1) * xs + one);
-}
-
 // The fit of every series, slice by slice, in the handle's regress workspace. A slice of n series holds, per series:
 // the ARX design ((C + 1) R doubles), the flat-differenced regressors (k T; one copy for the whole call when the matrix
 // is shared), the differenced series, the ARX and Hannan-Rissanen results and the start point. With user_init only the
@@ -2033,12 +1966,8 @@ int arimax_fit_dev(arima_handle *h, const AxShape &a, const double *y, int64_t l
     const int R = design ? dsg.rows() : 0, C = design ? dsg.cols() : 0;
     const int64_t per_series = (design ? (int64_t)(C + 1) * R + (xs ? kT : 0) : 0) + ldn +
                                (start ? (int64_t)Ka + Kh + Kp + 2 : 0);
-    int64_t slice_bytes = h->regress_slice_bytes;
-    if (slice_bytes <= 0) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(h, hipMemGetInfo(&free_b, &total_b));
-        slice_bytes = std::max<int64_t>(1ll << 30, (int64_t)((free_b + h->rg_ws.bytes) / 10 * 6));
-    }
+    int64_t slice_bytes;
+    PASSCHK(auto_slice_bytes(h, h->regress_slice_bytes, h->rg_ws.bytes, &slice_bytes));
     const int64_t slice = sts::plan::regress_slice_rows(slice_bytes, per_series), ns = std::min(slice, N);
     // (the differenced rows behind them stay 128-byte aligned)
     const int64_t ws_d = design ? sts::rg_ws_doubles(ns, R, C) : 0, dx_d = design ? round_up(xs ? ns * kT : kT, 16) : 0;
@@ -2108,34 +2037,35 @@ int arima_arimax_num_coef(int32_t n_xcols, int32_t p, int32_t q, int32_t xreg_ma
     return K > INT32_MAX ? ARIMA_E_INVALID_ARG : (int)K;
 }
 
+static int arimax_fit_body(arima_handle *h, CallFlavour flavour, const double *series, int64_t N, int64_t ld,
+                           const double *xreg, int64_t xs, const AxShape &a, const double *user_init, double *coef_out,
+                           double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out,
+                           void *stream) {
+    if (!h) return ARIMA_E_INVALID_ARG;
+    CallFrame f(h, flavour);
+    bool done;
+    PASSCHK(arimax_check(h, a, N, ld, xs, a.T, &done));
+    if (done) return ARIMA_OK;
+    const int64_t nd = N * (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t), coef_bytes = nd * a.num_coef();
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, a.T), a.T > 0), x_block(xreg, (int64_t)a.k * a.T, N, xs),
+                    buf_in(user_init, coef_bytes, false), buf_out(coef_out, coef_bytes), buf_out(ll_out, nd),
+                    buf_out(status_out, ni), buf_opt_out(n_eval_out, ni), buf_opt_out(n_grad_out, ni)}));
+    PASSCHK(f.overlap());
+    PASSCHK(f.begin(stream));
+    const sts::FitOut o{f.dev<double>(3), f.dev<double>(4), f.dev<int32_t>(5), f.dev<int32_t>(6), f.dev<int32_t>(7),
+                        nullptr};
+    PASSCHK(arimax_fit_dev(h, a, f.dev<double>(0), ld, f.dev<double>(1), xs, N, f.dev<double>(2), o, f.s()));
+    return f.finish();
+}
+
 int arima_arimax_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *xreg,
                            int64_t x_series_stride, int32_t n_xcols, int32_t p, int32_t d, int32_t q,
                            int32_t xreg_max_lag, int32_t include_original_xreg, int32_t include_intercept,
                            const double *user_init, double *coef_out, double *ll_out, int32_t *status_out,
                            int32_t *n_eval_out, int32_t *n_grad_out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
-    bool done;
-    PASSCHK(arimax_check(h, a, N, T, x_series_stride, T, &done));
-    if (done) return ARIMA_OK;
-    if ((T > 0 && (!series || !xreg)) || !coef_out || !ll_out || !status_out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t nd = (size_t)N * sizeof(double), ni = (size_t)N * sizeof(int32_t), row_bytes = nd * T,
-                 x_bytes = (size_t)arimax_x_doubles(a, N, x_series_stride, T) * sizeof(double),
-                 coef_bytes = nd * (size_t)a.num_coef(), ui_bytes = user_init ? coef_bytes : 0;
-    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(user_init, ui_bytes)},
-                          {ByteSpan(coef_out, coef_bytes), ByteSpan(ll_out, nd), ByteSpan(status_out, ni),
-                           ByteSpan(n_eval_out, n_eval_out ? ni : 0), ByteSpan(n_grad_out, n_grad_out ? ni : 0)}));
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(user_init, ui_bytes),
-                     stage_out(coef_out, coef_bytes), stage_out(ll_out, nd), stage_out(status_out, ni),
-                     stage_optional_out(n_eval_out, ni), stage_optional_out(n_grad_out, ni)}));
-    const sts::FitOut o{f.dev<double>(3), f.dev<double>(4), f.dev<int32_t>(5), f.dev<int32_t>(6), f.dev<int32_t>(7),
-                        nullptr};
-    PASSCHK(arimax_fit_dev(h, a, f.dev<double>(0), T, f.dev<double>(1), x_series_stride, N,
-                           user_init ? f.dev<double>(2) : nullptr, o, f.s()));
-    return f.finish();
+    return arimax_fit_body(h, kHostBuffers, series, N, T, xreg, x_series_stride,
+                           {T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0},
+                           user_init, coef_out, ll_out, status_out, n_eval_out, n_grad_out, nullptr);
 }
 
 int arima_arimax_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
@@ -2144,24 +2074,30 @@ int arima_arimax_fit_batch_device(arima_handle *h, const double *d_series, int64
                                   int32_t include_intercept, const double *d_user_init, double *d_coef_out,
                                   double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
                                   int32_t *d_n_grad_out, void *stream) {
+    return arimax_fit_body(h, kDeviceBuffers, d_series, N, ld, d_xreg, x_series_stride,
+                           {T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0},
+                           d_user_init, d_coef_out, d_ll_out, d_status_out, d_n_eval_out, d_n_grad_out, stream);
+}
+
+static int arimax_forecast_body(arima_handle *h, CallFlavour flavour, const double *series, int64_t N, int64_t ld,
+                                const double *xreg, int64_t xs, int32_t n_future, const AxShape &a, const double *coef,
+                                double *out, int64_t ld_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
+    CallFrame f(h, flavour);
     bool done;
-    PASSCHK(arimax_check(h, a, N, ld, x_series_stride, T, &done));
-    if (done) return ARIMA_OK;
-    if ((T > 0 && (!d_series || !d_xreg)) || !d_coef_out || !d_ll_out || !d_status_out)
-        return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int64_t sd = (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t), coef_bytes = N * a.num_coef() * sd;
-    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
-                              ByteSpan(d_xreg, arimax_x_doubles(a, N, x_series_stride, T) * sd),
-                              ByteSpan(d_user_init, d_user_init ? coef_bytes : 0)},
-                          {ByteSpan(d_coef_out, coef_bytes), ByteSpan(d_ll_out, N * sd), ByteSpan(d_status_out, ni),
-                           ByteSpan(d_n_eval_out, d_n_eval_out ? ni : 0),
-                           ByteSpan(d_n_grad_out, d_n_grad_out ? ni : 0)}));
+    PASSCHK(arimax_check(h, a, N, ld, xs, n_future, &done));
+    if (ld_out < a.T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
+    PASSCHK(arimax_forecast_check(h, a, n_future));
+    if (done || a.T == 0) return ARIMA_OK;
+    // (the regressor block is needed also when there is no future row to read)
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, a.T)),
+                    buf_in(xreg, x_block(xreg, (int64_t)a.k * n_future, N, xs).bytes),
+                    buf_in(coef, N * a.num_coef() * (int64_t)sizeof(double)),
+                    buf_out(out, strided_bytes(N, ld_out, a.T))}));
+    PASSCHK(f.overlap());
     PASSCHK(f.begin(stream));
-    const sts::FitOut o{d_coef_out, d_ll_out, d_status_out, d_n_eval_out, d_n_grad_out, nullptr};
-    PASSCHK(arimax_fit_dev(h, a, d_series, ld, d_xreg, x_series_stride, N, d_user_init, o, f.s()));
+    PASSCHK(arimax_forecast_dev(h, a, f.dev<double>(0), ld, f.dev<double>(1), xs, n_future, f.dev<double>(2),
+                                f.dev<double>(3), ld_out, N, f.s()));
     return f.finish();
 }
 
@@ -2169,25 +2105,9 @@ int arima_arimax_forecast_batch(arima_handle *h, const double *series, int64_t N
                                 int64_t x_series_stride, int32_t n_xcols, int32_t n_future, int32_t p, int32_t d,
                                 int32_t q, int32_t xreg_max_lag, int32_t include_original_xreg,
                                 int32_t include_intercept, const double *coef, double *out) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
-    bool done;
-    PASSCHK(arimax_check(h, a, N, T, x_series_stride, n_future, &done));
-    PASSCHK(arimax_forecast_check(h, a, n_future));
-    if (done || T == 0) return ARIMA_OK;
-    if (!series || !xreg || !coef || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const size_t nd = (size_t)N * sizeof(double), row_bytes = nd * T,
-                 x_bytes = (size_t)arimax_x_doubles(a, N, x_series_stride, n_future) * sizeof(double),
-                 coef_bytes = nd * (size_t)a.num_coef();
-    PASSCHK(check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(xreg, x_bytes), ByteSpan(coef, coef_bytes)},
-                          {ByteSpan(out, row_bytes)}));
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(xreg, x_bytes), stage_in(coef, coef_bytes),
-                     stage_out(out, row_bytes)}));
-    PASSCHK(arimax_forecast_dev(h, a, f.dev<double>(0), T, f.dev<double>(1), x_series_stride, n_future,
-                                f.dev<double>(2), f.dev<double>(3), T, N, f.s()));
-    return f.finish();
+    return arimax_forecast_body(h, kHostBuffers, series, N, T, xreg, x_series_stride, n_future,
+                                {T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0,
+                                 include_intercept ? 1 : 0}, coef, out, T, nullptr);
 }
 
 int arima_arimax_forecast_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
@@ -2195,24 +2115,11 @@ int arima_arimax_forecast_batch_device(arima_handle *h, const double *d_series, 
                                        int32_t n_future, int32_t p, int32_t d, int32_t q, int32_t xreg_max_lag,
                                        int32_t include_original_xreg, int32_t include_intercept, const double *d_coef,
                                        double *d_out, int64_t ld_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
-    const AxShape a{T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0, include_intercept ? 1 : 0};
-    bool done;
-    PASSCHK(arimax_check(h, a, N, ld, x_series_stride, n_future, &done));
-    if (ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    PASSCHK(arimax_forecast_check(h, a, n_future));
-    if (done || T == 0) return ARIMA_OK;
-    if (!d_series || !d_xreg || !d_coef || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int64_t sd = (int64_t)sizeof(double);
-    PASSCHK(check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * sd),
-                              ByteSpan(d_xreg, arimax_x_doubles(a, N, x_series_stride, n_future) * sd),
-                              ByteSpan(d_coef, N * a.num_coef() * sd)},
-                          {ByteSpan(d_out, ((N - 1) * ld_out + T) * sd)}));
-    PASSCHK(f.begin(stream));
-    PASSCHK(arimax_forecast_dev(h, a, d_series, ld, d_xreg, x_series_stride, n_future, d_coef, d_out, ld_out, N, f.s()));
-    return f.finish();
+    return arimax_forecast_body(h, kDeviceBuffers, d_series, N, ld, d_xreg, x_series_stride, n_future,
+                                {T, n_xcols, p, d, q, xreg_max_lag, include_original_xreg ? 1 : 0,
+                                 include_intercept ? 1 : 0}, d_coef, d_out, ld_out, stream);
 }
+
 
 // ---------------------------------------------------------------------------------------------------------
 // order search over (d, p, q, intercept) — SURVEY.md 8(f) row 2 (config C5)
@@ -2437,8 +2344,8 @@ int arima_order_search_batch(arima_handle *h, const double *series, int64_t N, i
     if (!series || !order_out || !coef_out || !aic_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     PASSCHK(f.begin());
     const size_t nd = (size_t)N * sizeof(double);
-    PASSCHK(f.stage({stage_in(series, nd * T), stage_out(order_out, (size_t)N * 4 * sizeof(int32_t)),
-                     stage_out(coef_out, 11 * nd), stage_out(aic_out, nd)}));
+    PASSCHK(f.stage({buf_in(series, nd * T), buf_out(order_out, (size_t)N * 4 * sizeof(int32_t)),
+                     buf_out(coef_out, 11 * nd), buf_out(aic_out, nd)}));
     int rc = order_search_locked(h, f.dev<double>(0), N, T, T, max_p, max_d, max_q, intercept_mode, method,
                                  f.dev<int32_t>(1), f.dev<double>(2), f.dev<double>(3), nullptr, f.s());
     join_lanes(h, f.s());
@@ -2664,8 +2571,8 @@ int arima_autofit_batch(arima_handle *h, const double *series, int64_t N, int32_
     if (!series || !order_out || !coef_out || !aic_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     PASSCHK(f.begin());
     const size_t ni = (size_t)N * sizeof(int32_t), nd = (size_t)N * sizeof(double);
-    PASSCHK(f.stage({stage_in(series, nd * T), stage_out(order_out, 4 * ni), stage_out(coef_out, 11 * nd),
-                     stage_out(aic_out, nd), stage_out(status_out, ni), stage_optional_out(n_fits_out, ni)}));
+    PASSCHK(f.stage({buf_in(series, nd * T), buf_out(order_out, 4 * ni), buf_out(coef_out, 11 * nd),
+                     buf_out(aic_out, nd), buf_out(status_out, ni), buf_opt_out(n_fits_out, ni)}));
     int rc = autofit_locked(h, f.dev<double>(0), N, T, T, max_p, max_d, max_q, f.dev<int32_t>(1), f.dev<double>(2),
                             f.dev<double>(3), f.dev<int32_t>(4), f.dev<int32_t>(5), f.s(), nullptr);
     rc = f.finish(rc);
@@ -2683,7 +2590,7 @@ int arima_kpss_batch(arima_handle *h, const double *series, int64_t N, int32_t T
     if (st == ARIMA_ST_OK) {
         int64_t ld = 0;
         RCCHK(h, upload_padded(h, series, N, T, &ld, f.s()), "upload");
-        PASSCHK(f.stage({stage_out(stat_out, (size_t)N * sizeof(double))}));
+        PASSCHK(f.stage({buf_out(stat_out, (size_t)N * sizeof(double))}));
         RCCHK(h, sts::launch_kpss_c(h->diff.as<double>(), ld, T, N, 0, nullptr, f.dev<double>(0), f.s()), "kpss");
     }
     PASSCHK(f.finish());
@@ -2734,44 +2641,21 @@ int md_fit_launch(arima_handle *h, int model, const double *rows, int64_t ld, in
     return ARIMA_OK;
 }
 
-int md_fit_host(arima_handle *h, int model, const double *series, int64_t N, int32_t T, double *coef_out,
-                double *obj_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
+int md_fit_body(arima_handle *h, CallFlavour flavour, int model, const double *series, int64_t N, int32_t T, int64_t ld,
+                double *coef_out, double *obj_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out,
+                void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    if (N == 0) return ARIMA_OK;
-    if (!series || !coef_out || !obj_out || !status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = sts::model_num_params(model);
-    const size_t row_bytes = (size_t)N * T * sizeof(double), nd = (size_t)N * sizeof(double),
-                 ni = (size_t)N * sizeof(int32_t);
-    RCCHK(h, check_overlap(h, {ByteSpan(series, row_bytes)},
-                           {ByteSpan(coef_out, nd * K), ByteSpan(obj_out, nd), ByteSpan(status_out, ni),
-                            ByteSpan(n_eval_out, ni), ByteSpan(n_grad_out, ni)}), "overlap");
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_out(coef_out, nd * K), stage_out(obj_out, nd),
-                     stage_out(status_out, ni), stage_optional_out(n_eval_out, ni),
-                     stage_optional_out(n_grad_out, ni)}));
-    RCCHK(h, md_fit_launch(h, model, f.dev<double>(0), T, N, T, f.dev<double>(1), f.dev<double>(2), f.dev<int32_t>(3),
-                           f.dev<int32_t>(4), f.dev<int32_t>(5), f.s()), "fit");
-    return f.finish();
-}
-
-int md_fit_device(arima_handle *h, int model, const double *d_series, int64_t N, int32_t T, int64_t ld,
-                  double *d_coef_out, double *d_obj_out, int32_t *d_status_out, int32_t *d_n_eval_out,
-                  int32_t *d_n_grad_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
+    CallFrame f(h, flavour);
     if (N < 0 || T < 1 || ld < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
-    if (!d_series || !d_coef_out || !d_obj_out || !d_status_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = sts::model_num_params(model);
-    const size_t nd = (size_t)N * sizeof(double), ni = (size_t)N * sizeof(int32_t);
-    RCCHK(h, check_overlap(h, {ByteSpan(d_series, ((N - 1) * ld + T) * (int64_t)sizeof(double))},
-                           {ByteSpan(d_coef_out, nd * K), ByteSpan(d_obj_out, nd), ByteSpan(d_status_out, ni),
-                            ByteSpan(d_n_eval_out, ni), ByteSpan(d_n_grad_out, ni)}), "overlap");
+    const int64_t nd = N * (int64_t)sizeof(double), ni = N * (int64_t)sizeof(int32_t);
+    PASSCHK(f.bind({buf_in(series, strided_bytes(N, ld, T)), buf_out(coef_out, nd * sts::model_num_params(model)),
+                    buf_out(obj_out, nd), buf_out(status_out, ni), buf_opt_out(n_eval_out, ni),
+                    buf_opt_out(n_grad_out, ni)}));
+    RCCHK(h, f.overlap(), "overlap");
     PASSCHK(f.begin(stream));
-    RCCHK(h, md_fit_launch(h, model, d_series, ld, N, T, d_coef_out, d_obj_out, d_status_out, d_n_eval_out,
-                           d_n_grad_out, f.s()), "fit");
+    RCCHK(h, md_fit_launch(h, model, f.dev<double>(0), ld, N, T, f.dev<double>(1), f.dev<double>(2), f.dev<int32_t>(3),
+                           f.dev<int32_t>(4), f.dev<int32_t>(5), f.s()), "fit");
     return f.finish();
 }
 
@@ -2782,14 +2666,11 @@ int md_eval_host(arima_handle *h, int model, const double *series, int64_t N, in
     CallFrame f(h, kHostBuffers);
     if (N < 0 || T < 1) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     if (N == 0) return ARIMA_OK;
-    if (!series || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
     const int K = sts::model_num_params(model);
-    const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
-    const size_t out_bytes = (size_t)N * (want_grad ? K : 1) * sizeof(double);
-    RCCHK(h, check_overlap(h, {ByteSpan(series, row_bytes), ByteSpan(params, par_bytes)}, {ByteSpan(out, out_bytes)}),
-          "overlap");
+    const int64_t nd = N * (int64_t)sizeof(double);
+    PASSCHK(f.bind({buf_in(series, nd * T), buf_in(params, nd * K), buf_out(out, nd * (want_grad ? K : 1))}));
+    RCCHK(h, f.overlap(), "overlap");
     PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(series, row_bytes), stage_in(params, par_bytes), stage_out(out, out_bytes)}));
     RCCHK(h, sts::launch_model_eval(model, f.dev<double>(0), T, N, T, f.dev<double>(1),
                                     want_grad ? nullptr : f.dev<double>(2), want_grad ? f.dev<double>(2) : nullptr,
                                     f.s()), "model eval");
@@ -2815,72 +2696,46 @@ int fx_launch(const FxKind &k, const double *in, int64_t ld_in, const double *pa
     return sts::launch_model_effects(k.model, in, ld_in, params, out, ld_out, N, T, k.add, s);
 }
 
-int fx_host(arima_handle *h, const FxKind &k, const double *in_rows, int64_t N, int32_t T, const double *params,
-                    double *out) {
+int fx_body(arima_handle *h, CallFlavour flavour, const FxKind &k, const double *in, int64_t N, int32_t T, int64_t ld,
+            const double *params, double *out, int64_t ld_out, void *stream) {
     if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kHostBuffers);
-    if (N < 0 || T < 0) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
-    PASSCHK(fx_check(h, k));
-    if (N == 0 || T == 0) return ARIMA_OK;
-    if (!in_rows || !params || !out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = k.num_params();
-    const size_t row_bytes = (size_t)N * T * sizeof(double), par_bytes = (size_t)N * K * sizeof(double);
-    RCCHK(h, check_overlap(h, {ByteSpan(in_rows, row_bytes), ByteSpan(params, par_bytes)}, {ByteSpan(out, row_bytes)}),
-          "overlap");
-    PASSCHK(f.begin());
-    PASSCHK(f.stage({stage_in(in_rows, row_bytes), stage_in(params, par_bytes), stage_out(out, row_bytes)}));
-    RCCHK(h, fx_launch(k, f.dev<double>(0), T, f.dev<double>(1), f.dev<double>(2), T, N, T, f.s()), "model effects");
-    return f.finish();
-}
-
-int fx_device(arima_handle *h, const FxKind &k, const double *d_in, int64_t N, int32_t T, int64_t ld,
-                      const double *d_params, double *d_out, int64_t ld_out, void *stream) {
-    if (!h) return ARIMA_E_INVALID_ARG;
-    CallFrame f(h, kDeviceBuffers);
+    CallFrame f(h, flavour);
     if (N < 0 || T < 0 || ld < T || ld_out < T) return set_err(h, ARIMA_E_INVALID_ARG, "bad shape");
     PASSCHK(fx_check(h, k));
     if (N == 0 || T == 0) return ARIMA_OK;
-    if (!d_in || !d_params || !d_out) return set_err(h, ARIMA_E_INVALID_ARG, "null buffer");
-    const int K = k.num_params();
-    RCCHK(h, check_overlap(h, {ByteSpan(d_in, ((N - 1) * ld + T) * (int64_t)sizeof(double)),
-                               ByteSpan(d_params, N * K * (int64_t)sizeof(double))},
-                           {ByteSpan(d_out, ((N - 1) * ld_out + T) * (int64_t)sizeof(double))}), "overlap");
+    PASSCHK(f.bind({buf_in(in, strided_bytes(N, ld, T)), buf_in(params, N * k.num_params() * (int64_t)sizeof(double)),
+                    buf_out(out, strided_bytes(N, ld_out, T))}));
+    RCCHK(h, f.overlap(), "overlap");
     PASSCHK(f.begin(stream));
-    RCCHK(h, fx_launch(k, d_in, ld, d_params, d_out, ld_out, N, T, f.s()), "model effects");
+    RCCHK(h, fx_launch(k, f.dev<double>(0), ld, f.dev<double>(1), f.dev<double>(2), ld_out, N, T, f.s()),
+          "model effects");
     return f.finish();
-}
-// the pairs of EWMA / GARCH / ARGARCH
-int md_effects_host(arima_handle *h, int model, const double *in_rows, int64_t N, int32_t T, const double *params,
-                    double *out, int add) {
-    return fx_host(h, FxKind{kFxPair, model, 0, add}, in_rows, N, T, params, out);
-}
-int md_effects_device(arima_handle *h, int model, const double *d_in, int64_t N, int32_t T, int64_t ld,
-                      const double *d_params, double *d_out, int64_t ld_out, void *stream, int add) {
-    return fx_device(h, FxKind{kFxPair, model, 0, add}, d_in, N, T, ld, d_params, d_out, ld_out, stream);
 }
 }  // namespace
 
 int arima_ewma_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *smoothing_out,
                          double *sse_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
-    return md_fit_host(h, sts::kModelEwma, series, N, T, smoothing_out, sse_out, status_out, n_eval_out, n_grad_out);
+    return md_fit_body(h, kHostBuffers, sts::kModelEwma, series, N, T, T, smoothing_out, sse_out, status_out, n_eval_out,
+                       n_grad_out, nullptr);
 }
 
 int arima_ewma_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                 double *d_smoothing_out, double *d_sse_out, int32_t *d_status_out,
                                 int32_t *d_n_eval_out, int32_t *d_n_grad_out, void *stream) {
-    return md_fit_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing_out, d_sse_out, d_status_out,
+    return md_fit_body(h, kDeviceBuffers, sts::kModelEwma, d_series, N, T, ld, d_smoothing_out, d_sse_out, d_status_out,
                          d_n_eval_out, d_n_grad_out, stream);
 }
 
 int arima_garch_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *coef_out,
                           double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
-    return md_fit_host(h, sts::kModelGarch, series, N, T, coef_out, ll_out, status_out, n_eval_out, n_grad_out);
+    return md_fit_body(h, kHostBuffers, sts::kModelGarch, series, N, T, T, coef_out, ll_out, status_out, n_eval_out,
+                       n_grad_out, nullptr);
 }
 
 int arima_garch_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                  double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
                                  int32_t *d_n_grad_out, void *stream) {
-    return md_fit_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
+    return md_fit_body(h, kDeviceBuffers, sts::kModelGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
                          d_n_grad_out, stream);
 }
 
@@ -2906,112 +2761,119 @@ int arima_garch_gradient_batch(arima_handle *h, const double *series, int64_t N,
 
 int arima_ewma_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T,
                                     const double *smoothing, double *out) {
-    return md_effects_host(h, sts::kModelEwma, series, N, T, smoothing, out, 0);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelEwma, 0, 0}, series, N, T, T, smoothing, out, T, nullptr);
 }
 
 int arima_ewma_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *smoothing,
                                  double *out) {
-    return md_effects_host(h, sts::kModelEwma, series, N, T, smoothing, out, 1);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelEwma, 0, 1}, series, N, T, T, smoothing, out, T, nullptr);
 }
 
 int arima_garch_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
                                      double *out) {
-    return md_effects_host(h, sts::kModelGarch, series, N, T, coef, out, 0);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelGarch, 0, 0}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_garch_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
                                   double *out) {
-    return md_effects_host(h, sts::kModelGarch, series, N, T, coef, out, 1);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelGarch, 0, 1}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_ewma_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                            const double *d_smoothing, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing, d_out, ld_out, stream, 0);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelEwma, 0, 0}, d_series, N, T, ld, d_smoothing, d_out, ld_out,
+                   stream);
 }
 
 int arima_ewma_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                         const double *d_smoothing, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelEwma, d_series, N, T, ld, d_smoothing, d_out, ld_out, stream, 1);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelEwma, 0, 1}, d_series, N, T, ld, d_smoothing, d_out, ld_out,
+                   stream);
 }
 
 int arima_garch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                             const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 0);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelGarch, 0, 0}, d_series, N, T, ld, d_coef, d_out, ld_out,
+                   stream);
 }
 
 int arima_garch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                          const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 1);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelGarch, 0, 1}, d_series, N, T, ld, d_coef, d_out, ld_out,
+                   stream);
 }
 
 int arima_argarch_fit_batch(arima_handle *h, const double *series, int64_t N, int32_t T, double *coef_out,
                             double *ll_out, int32_t *status_out, int32_t *n_eval_out, int32_t *n_grad_out) {
-    return md_fit_host(h, sts::kModelArGarch, series, N, T, coef_out, ll_out, status_out, n_eval_out, n_grad_out);
+    return md_fit_body(h, kHostBuffers, sts::kModelArGarch, series, N, T, T, coef_out, ll_out, status_out, n_eval_out,
+                       n_grad_out, nullptr);
 }
 
 int arima_argarch_fit_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                    double *d_coef_out, double *d_ll_out, int32_t *d_status_out, int32_t *d_n_eval_out,
                                    int32_t *d_n_grad_out, void *stream) {
-    return md_fit_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
+    return md_fit_body(h, kDeviceBuffers, sts::kModelArGarch, d_series, N, T, ld, d_coef_out, d_ll_out, d_status_out, d_n_eval_out,
                          d_n_grad_out, stream);
 }
 
 int arima_argarch_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
                                        double *out) {
-    return md_effects_host(h, sts::kModelArGarch, series, N, T, coef, out, 0);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelArGarch, 0, 0}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_argarch_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, const double *coef,
                                     double *out) {
-    return md_effects_host(h, sts::kModelArGarch, series, N, T, coef, out, 1);
+    return fx_body(h, kHostBuffers, FxKind{kFxPair, sts::kModelArGarch, 0, 1}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_argarch_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                               const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 0);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelArGarch, 0, 0}, d_series, N, T, ld, d_coef, d_out, ld_out,
+                   stream);
 }
 
 int arima_argarch_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                            const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return md_effects_device(h, sts::kModelArGarch, d_series, N, T, ld, d_coef, d_out, ld_out, stream, 1);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxPair, sts::kModelArGarch, 0, 1}, d_series, N, T, ld, d_coef, d_out, ld_out,
+                   stream);
 }
 
 int arima_ar_remove_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
                                   const double *coef, double *out) {
-    return fx_host(h, FxKind{kFxArPair, 0, p, 0}, series, N, T, coef, out);
+    return fx_body(h, kHostBuffers, FxKind{kFxArPair, 0, p, 0}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_ar_add_effects_batch(arima_handle *h, const double *series, int64_t N, int32_t T, int32_t p,
                                const double *coef, double *out) {
-    return fx_host(h, FxKind{kFxArPair, 0, p, 1}, series, N, T, coef, out);
+    return fx_body(h, kHostBuffers, FxKind{kFxArPair, 0, p, 1}, series, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_ar_remove_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                          int32_t p, const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return fx_device(h, FxKind{kFxArPair, 0, p, 0}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxArPair, 0, p, 0}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
 }
 
 int arima_ar_add_effects_batch_device(arima_handle *h, const double *d_series, int64_t N, int32_t T, int64_t ld,
                                       int32_t p, const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return fx_device(h, FxKind{kFxArPair, 0, p, 1}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxArPair, 0, p, 1}, d_series, N, T, ld, d_coef, d_out, ld_out, stream);
 }
 
 int arima_garch_sample_batch(arima_handle *h, const double *z, int64_t N, int32_t T, const double *coef, double *out) {
-    return fx_host(h, FxKind{kFxSample, sts::kModelGarch, 0, 0}, z, N, T, coef, out);
+    return fx_body(h, kHostBuffers, FxKind{kFxSample, sts::kModelGarch, 0, 0}, z, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_argarch_sample_batch(arima_handle *h, const double *z, int64_t N, int32_t T, const double *coef, double *out) {
-    return fx_host(h, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, z, N, T, coef, out);
+    return fx_body(h, kHostBuffers, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, z, N, T, T, coef, out, T, nullptr);
 }
 
 int arima_garch_sample_batch_device(arima_handle *h, const double *d_z, int64_t N, int32_t T, int64_t ld,
                                     const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return fx_device(h, FxKind{kFxSample, sts::kModelGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out, stream);
+    return fx_body(h, kDeviceBuffers, FxKind{kFxSample, sts::kModelGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out, stream);
 }
 
 int arima_argarch_sample_batch_device(arima_handle *h, const double *d_z, int64_t N, int32_t T, int64_t ld,
                                       const double *d_coef, double *d_out, int64_t ld_out, void *stream) {
-    return fx_device(h, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out,
+    return fx_body(h, kDeviceBuffers, FxKind{kFxSample, sts::kModelArGarch, 0, 0}, d_z, N, T, ld, d_coef, d_out, ld_out,
                              stream);
 }
 

@@ -1,7 +1,8 @@
 // host_plan.hpp — the host-side sizing arithmetic of arima_runtime.cpp as pure functions: the host path's chunk
 // schedule, the layout of one chunk's results in pinned staging, the layout of a host-buffer call's staged arrays, the
-// byte-span overlap rule of the entry points, the partition par_memcpy hands its threads, and the rows per slice of the
-// sliced device fit, of the residual diagnostics and of the design-matrix regressions. No HIP headers: a CPU program
+// byte-span overlap rule of the entry points, the extent of a strided buffer and the buffer table the entry points
+// derive their null check, overlap check and staging from, the partition par_memcpy hands its threads, and the rows per
+// slice of the sliced device fit, of the residual diagnostics and of the design-matrix regressions. No HIP headers: a CPU program
 // includes this file and sweeps the functions (tests/sim/hostplan_sim.cpp). arima_runtime.cpp keeps no second copy of
 // the formulas.
 #pragma once
@@ -94,6 +95,51 @@ inline Overlap find_overlap(const ByteSpan *in, int n_in, const ByteSpan *out, i
             if (out[a].meets(out[b])) return kOutputsMeet;
     }
     return kDisjoint;
+}
+
+// Bytes a caller's N rows of `cols` elements span when consecutive rows start `ld` elements apart (ld >= cols): from the
+// first element of row 0 to the last of row N - 1. At ld == cols that is N * cols * size. No rows, or rows of no
+// elements, span nothing.
+inline int64_t strided_bytes(int64_t N, int64_t ld, int64_t cols, int64_t size = 8) {
+    return N <= 0 || cols <= 0 ? 0 : ((N - 1) * ld + cols) * size;
+}
+
+// One buffer argument of an entry point: where it is, how many bytes of it the call touches, what the call does with
+// it, and whether a null pointer is refused (`need`). An entry point writes its arguments down once as a table of these
+// (CallFrame in arima_runtime.cpp); the null check, the overlap rule and the staging of a host-buffer call all read it.
+enum BufRole : uint8_t { kBufIn, kBufOut, kBufOptOut, kBufInOut };
+struct Buf {
+    const void *p;
+    int64_t bytes;
+    BufRole role;
+    bool need;
+    bool read() const { return role == kBufIn || role == kBufInOut; }
+    bool written() const { return role != kBufIn; }
+};
+inline Buf buf_in(const void *p, int64_t bytes, bool need = true) { return {p, bytes, kBufIn, need}; }
+inline Buf buf_out(void *p, int64_t bytes) { return {p, bytes, kBufOut, true}; }
+inline Buf buf_opt_out(void *p, int64_t bytes) { return {p, bytes, kBufOptOut, false}; }   // null: not wanted
+inline Buf buf_inout(void *p, int64_t bytes) { return {p, bytes, kBufInOut, true}; }
+constexpr int kMaxBufs = 8;
+
+inline bool missing_buffer(const Buf *t, int n) {
+    for (int i = 0; i < n; ++i)
+        if (t[i].need && !t[i].p) return true;
+    return false;
+}
+
+// A table's two lists for find_overlap, in table order. Whatever the call writes is an output, an in-out buffer too:
+// that the call also reads it adds nothing to what an output may not meet.
+inline void split_spans(const Buf *t, int n, ByteSpan *in, int *n_in, ByteSpan *out, int *n_out) {
+    *n_in = *n_out = 0;
+    for (int i = 0; i < n; ++i)
+        (t[i].written() ? out[(*n_out)++] : in[(*n_in)++]) = ByteSpan(t[i].p, t[i].bytes);
+}
+inline Overlap table_overlap(const Buf *t, int n) {
+    ByteSpan in[kMaxBufs], out[kMaxBufs];
+    int n_in, n_out;
+    split_spans(t, n, in, &n_in, out, &n_out);
+    return find_overlap(in, n_in, out, n_out);
 }
 
 // The (offset, length) pieces par_memcpy copies, one per thread: at most `threads` of them, none below 4 MiB unless

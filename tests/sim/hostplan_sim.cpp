@@ -279,6 +279,80 @@ static void sweep_spans() {
                 " draws (%" PRId64 " refused)\n", pairs, draws, refused);
 }
 
+// strided_bytes against the elements themselves: one past the last byte of any element of N rows of `cols` elements
+// that start `ld` elements apart
+static void sweep_strided() {
+    int64_t cases = 0;
+    for (int64_t N : {0, 1, 2, 65})
+        for (int64_t cols : {0, 1, 12})
+            for (int64_t ld : {cols, cols + 1, cols + 4})
+                for (int64_t size : {1, 4, 8}) {
+                    int64_t end = 0;
+                    for (int64_t i = 0; i < N; ++i)
+                        for (int64_t j = 0; j < cols; ++j) end = std::max(end, (i * ld + j + 1) * size);
+                    const int64_t got = P::strided_bytes(N, ld, cols, size);
+                    if (got != end) FAIL("strided_bytes(%" PRId64 ", %" PRId64 ", %" PRId64 ", %" PRId64 ") = %" PRId64 ", the elements end at %" PRId64, N, ld, cols, size, got, end);
+                    if (ld == cols && got != N * cols * size) FAIL("strided_bytes: dense rows span %" PRId64 ", not N * cols * size", got);
+                    if (size == 8 && P::strided_bytes(N, ld, cols) != got) FAIL("strided_bytes: the default element is not a double");
+                    ++cases;
+                }
+    std::printf("strided_bytes: %" PRId64 " shapes equal the per-element enumeration\n", cases);
+}
+
+// A buffer table against find_overlap on lists built by hand: the same verdict and the same kind
+static void check_table(const char *what, const P::Buf *t, int n, const P::ByteSpan *in, int n_in, const P::ByteSpan *out,
+                        int n_out, P::Overlap want) {
+    const P::Overlap by_hand = P::find_overlap(in, n_in, out, n_out), got = P::table_overlap(t, n);
+    if (by_hand != want) FAIL("table %s: the hand-built lists give %d, the case expects %d", what, (int)by_hand, (int)want);
+    if (got != want) FAIL("table %s: table_overlap gives %d, expected %d", what, (int)got, (int)want);
+    P::ByteSpan si[P::kMaxBufs], so[P::kMaxBufs];
+    int ni = -1, no = -1;
+    P::split_spans(t, n, si, &ni, so, &no);
+    if (ni != n_in || no != n_out) FAIL("table %s: split into %d inputs and %d outputs, expected %d and %d", what, ni, no, n_in, n_out);
+    for (int i = 0; i < n_in; ++i)
+        if (si[i].lo != in[i].lo || si[i].hi != in[i].hi) FAIL("table %s: input %d differs from the hand-built span", what, i);
+    for (int i = 0; i < n_out; ++i)
+        if (so[i].lo != out[i].lo || so[i].hi != out[i].hi) FAIL("table %s: output %d differs from the hand-built span", what, i);
+}
+
+static void sweep_tables() {
+    static unsigned char a[256];
+    using P::ByteSpan;
+    {   // a null optional output meets nothing, whatever its size
+        const P::Buf t[] = {P::buf_in(a, 64), P::buf_out(a + 64, 32), P::buf_opt_out(nullptr, 64), P::buf_out(a + 96, 16)};
+        const ByteSpan in[] = {ByteSpan(a, 64)}, out[] = {ByteSpan(a + 64, 32), ByteSpan(nullptr, 64), ByteSpan(a + 96, 16)};
+        check_table("null optional output", t, 4, in, 1, out, 3, P::kDisjoint);
+        if (P::missing_buffer(t, 4)) FAIL("a null optional output counts as missing");
+    }
+    {   // ... and a wanted one is an output like any other
+        const P::Buf t[] = {P::buf_in(a, 64), P::buf_out(a + 64, 32), P::buf_opt_out(a + 80, 16)};
+        const ByteSpan in[] = {ByteSpan(a, 64)}, out[] = {ByteSpan(a + 64, 32), ByteSpan(a + 80, 16)};
+        check_table("optional output on an output", t, 3, in, 1, out, 2, P::kOutputsMeet);
+    }
+    {   // a zero-byte input inside an output is no overlap; the input behind it is one
+        const P::Buf t[] = {P::buf_in(a + 70, 0, false), P::buf_out(a + 64, 32), P::buf_in(a + 90, 8)};
+        const ByteSpan in[] = {ByteSpan(a + 70, 0), ByteSpan(a + 90, 8)}, out[] = {ByteSpan(a + 64, 32)};
+        check_table("zero-byte input", t, 2, in, 1, out, 1, P::kDisjoint);
+        check_table("zero-byte input, then a real one", t, 3, in, 2, out, 1, P::kOutputMeetsInput);
+    }
+    {   // an in-out row is written: it may meet neither an input nor another output
+        const P::Buf alone[] = {P::buf_in(a, 64), P::buf_inout(a + 64, 64), P::buf_out(a + 128, 8)};
+        const ByteSpan in[] = {ByteSpan(a, 64)}, out[] = {ByteSpan(a + 64, 64), ByteSpan(a + 128, 8)};
+        check_table("in-out", alone, 3, in, 1, out, 2, P::kDisjoint);
+        const P::Buf on_in[] = {P::buf_in(a, 64), P::buf_inout(a + 56, 64), P::buf_out(a + 128, 8)};
+        const ByteSpan out2[] = {ByteSpan(a + 56, 64), ByteSpan(a + 128, 8)};
+        check_table("in-out on an input", on_in, 3, in, 1, out2, 2, P::kOutputMeetsInput);
+        const P::Buf on_out[] = {P::buf_in(a, 64), P::buf_inout(a + 64, 64), P::buf_out(a + 120, 8)};
+        const ByteSpan out3[] = {ByteSpan(a + 64, 64), ByteSpan(a + 120, 8)};
+        check_table("in-out on an output", on_out, 3, in, 1, out3, 2, P::kOutputsMeet);
+    }
+    {   // a needed buffer that is null is missing, an unneeded one is not
+        const P::Buf t[] = {P::buf_in(nullptr, 8, false), P::buf_out(a, 8)}, u[] = {P::buf_in(a, 8), P::buf_out(nullptr, 8)};
+        if (P::missing_buffer(t, 2) || !P::missing_buffer(u, 2)) FAIL("missing_buffer: needed and unneeded null buffers");
+    }
+    std::printf("buffer tables: split and overlap equal find_overlap on hand-built lists (null optional output, zero-byte input, in-out)\n");
+}
+
 static void sweep_memcpy() {
     const size_t MiB = size_t(1) << 20;
     const size_t sizes_b[] = {0, 1, 63, 64, 65, 4 * MiB - 1, 4 * MiB, 8 * MiB, 8 * MiB + 1, 37 * MiB + 13};
@@ -341,6 +415,8 @@ int main() {
     sweep_pin_layout();
     sweep_arena_layout();
     sweep_spans();
+    sweep_strided();
+    sweep_tables();
     sweep_memcpy();
     sweep_slices();
     std::printf("hostplan OK\n");

@@ -13,7 +13,9 @@ from types import SimpleNamespace as NS
 import numpy as np
 import pytest
 
+import arimax_ref as AXR
 import oracle as O
+import regarima_ref as CO
 import regress_ref as RR
 import smallfit_ref as R
 import sparkts_amd._lib as L
@@ -146,7 +148,7 @@ def _model_specs():
 # The regressions over a regressor matrix: k = 2 columns, AutoregressionX(yMaxLag 1, xMaxLag 1, includeOriginalX) has
 # K = 5 predictors and R = 11 rows, bgtest max_lag 3. The faults in the order regress_check and its callers test them.
 RG = NS(k=2, yl=1, xl=1, K=5, R=S.T - 1, xs_h=2 * S.T, xs_d=2 * S.T + 4, ldo=S.T + 2)
-RG_OVERLAP = ("an output overlaps an input", "outputs overlap")       # check_overlap's two messages, passed through
+RG_OVERLAP = ("an output overlaps an input", "outputs overlap")       # the overlap rule's two messages, passed through
 
 
 def _regress_specs():
@@ -193,6 +195,111 @@ def _regress_specs():
                         shape + [("n_xcols 0", dict(k=0), INVALID, "n_xcols < 1")] + stride +
                         [("65 columns", dict(k=64, xs=0), UNSUPPORTED, wide)],            # 1 + 64, one shared matrix
                         overlap=RG_OVERLAP))
+    return out
+
+
+# RegressionARIMA's Cochrane-Orcutt fit over the same k = 2 regressor block: co_check tests max_iter, then n_xcols,
+# then regress_check's rules, then its own width (the ones column is always there, so 64 regressors are one too many).
+def _regarima_specs():
+    out = []
+    for device in (False, True):
+        sfx, xs = ("_device", RG.xs_d) if device else ("", RG.xs_h)
+        args = [B("rows", "in", ROWS_D if device else ROWS_H), V("N", S.N), V("T", S.T)] + \
+            ([V("ld", S.ld)] if device else []) + \
+            [B("xreg", "in", ((S.N - 1) * xs + RG.k * S.T) * 8), V("xs", xs), V("k", RG.k), V("iters", 5),
+             B("coef", "out", ND * (1 + RG.k)), B("rho", "out", ND), B("n_iter", "out", NI, False),
+             B("status", "out", NI)] + ([V("stream", None)] if device else [])
+        wide = "at most 64 columns"
+        out.append(spec("arima_regarima_co_fit_batch" + sfx, device, args,
+                        [("max_iter 0", dict(iters=0), INVALID, "max_iter < 1"),
+                         ("max_iter before n_xcols", dict(iters=0, k=0), INVALID, "max_iter < 1"),
+                         ("n_xcols 0", dict(k=0), INVALID, "n_xcols < 1"),
+                         ("n_xcols < 0", dict(k=-1), INVALID, "n_xcols < 1"),
+                         ("n_xcols before the shape", dict(k=0, N=-1), INVALID, "n_xcols < 1"),
+                         ("N < 0", dict(N=-1), INVALID, "bad shape"), ("T < 0", dict(T=-1), INVALID, "bad shape")] +
+                        ([("ld < T", dict(ld=S.T - 1), INVALID, "bad shape")] if device else []) +
+                        [("x_series_stride below n_xcols * T", dict(xs=RG.k * S.T - 1), INVALID,
+                          "x_series_stride below n_xcols * T"),
+                         ("the stride before the columns", dict(xs=1, k=64), INVALID, "x_series_stride below n_xcols * T"),
+                         ("65 regressors", dict(k=65, xs=0), UNSUPPORTED, wide),          # regress_check's own count
+                         ("64 regressors and the ones column", dict(k=64, xs=0), UNSUPPORTED, wide),
+                         ("65 columns at N = 0", dict(k=64, xs=0, N=0), UNSUPPORTED, wide)],
+                        overlap=RG_OVERLAP))
+    return out
+
+
+# ARIMAX(1, 1, 1) with xreg_max_lag 1 and the original columns over k = 2 regressors: K' = 1 + 1 + 1 + 2 + 2 = 7
+# coefficients; the forecast reads n_future = 4 regressor rows. The faults in the order arimax_check, the device
+# forecast's own ld_out test and arimax_forecast_check test them.
+AX = NS(p=1, d=1, q=1, L=1, Kp=7, xs_h=RG.k * S.nf, xs_d=RG.k * S.nf + 4)
+AX_ORDERS = [V("p", AX.p), V("d", AX.d), V("q", AX.q), V("L", AX.L), V("orig", 1), V("I", 1)]
+AX_STRIDE = "x_series_stride below one matrix"
+
+
+def _arimax_faults(device, forecast):
+    """arimax_check's refusals; the rows of a regressor matrix are T for a fit and n_future for a forecast."""
+    huge = dict(T=10 ** 9, ld=10 ** 9, ldo=10 ** 9, k=1, xs=0)       # (d + 2) T alone is beyond an int
+    return [("N < 0", dict(N=-1), INVALID, "bad shape"), ("T < 0", dict(T=-1), INVALID, "bad shape")] + \
+        ([("ld < T", dict(ld=S.T - 1), INVALID, "bad shape")] if device else []) + \
+        ([("n_future < 0", dict(nf=-1), INVALID, "bad shape")] if forecast else []) + \
+        [("the shape before n_xcols", dict(N=-1, k=0), INVALID, "bad shape"),
+         ("n_xcols 0", dict(k=0), INVALID, "n_xcols < 1"),
+         ("n_xcols before the orders", dict(k=-1, p=-1), INVALID, "n_xcols < 1"),
+         ("p < 0", dict(p=-1), INVALID, "negative order or lag"), ("d < 0", dict(d=-1), INVALID, "negative order or lag"),
+         ("q < 0", dict(q=-1), INVALID, "negative order or lag"),
+         ("xreg_max_lag < 0", dict(L=-1), INVALID, "negative order or lag"),
+         ("the orders before the stride", dict(q=-1, xs=1), INVALID, "negative order or lag"),
+         ("x_series_stride below one matrix", dict(xs=RG.k * (S.nf if forecast else S.T) - 1), INVALID, AX_STRIDE),
+         ("the stride before p > 20", dict(xs=1, p=21), INVALID, AX_STRIDE),
+         ("p > 20", dict(p=21), UNSUPPORTED, "p, q <= 20"), ("q > 20", dict(q=21), UNSUPPORTED, "p, q <= 20"),
+         ("p > 20 before d > 16", dict(p=21, d=17), UNSUPPORTED, "p, q <= 20"),
+         ("d > 16", dict(d=17), UNSUPPORTED, "d <= 16"),
+         ("d > 16 before the coefficients", dict(d=17, L=20, xs=0), UNSUPPORTED, "d <= 16"),
+         ("45 coefficients", dict(L=20, xs=0), UNSUPPORTED, "at most 41 coefficients"),      # 3 + 2 * 20 + 2
+         ("45 coefficients at N = 0", dict(L=20, xs=0, N=0), UNSUPPORTED, "at most 41 coefficients"),
+         ("the regressor matrix beyond an int", dict(k=6 * 10 ** 8, L=0, orig=0, xs=0), UNSUPPORTED,
+          "regressor matrix too large")] + \
+        ([("the matrix before the series", dict(huge, nf=2 ** 31 - 1, k=2), UNSUPPORTED, "regressor matrix too large")]
+         if forecast else []) + \
+        [("the series beyond an int", huge, UNSUPPORTED, "series too long")]
+
+
+def _arimax_specs():
+    out = []
+    for device in (False, True):
+        sfx = "_device" if device else ""
+        rows = [B("rows", "in", ROWS_D if device else ROWS_H), V("N", S.N), V("T", S.T)] + \
+            ([V("ld", S.ld)] if device else [])
+        tail = [V("stream", None)] if device else []
+        xs = RG.xs_d if device else RG.xs_h
+        out.append(spec("arima_arimax_fit_batch" + sfx, device,
+                        rows + [B("xreg", "in", ((S.N - 1) * xs + RG.k * S.T) * 8), V("xs", xs), V("k", RG.k)] +
+                        AX_ORDERS + [B("user_init", "in", ND * AX.Kp, False), B("coef", "out", ND * AX.Kp),
+                                     B("ll", "out", ND), B("status", "out", NI), B("n_eval", "out", NI, False),
+                                     B("n_grad", "out", NI, False)] + tail,
+                        _arimax_faults(device, False), overlap=RG_OVERLAP))
+        xs = AX.xs_d if device else AX.xs_h
+        out.append(spec("arima_arimax_forecast_batch" + sfx, device,
+                        rows + [B("xreg", "in", ((S.N - 1) * xs + RG.k * S.nf) * 8), V("xs", xs), V("k", RG.k),
+                                V("nf", S.nf)] + AX_ORDERS +
+                        [B("coef", "in", ND * AX.Kp), B("out", "out", OUT_D if device else ROWS_H)] +
+                        ([V("ldo", S.ldo)] if device else []) + tail,
+                        _arimax_faults(device, True) +
+                        ([("ld_out < T", dict(ldo=S.T - 1), INVALID, "bad shape"),
+                          ("ld_out before the forecast's shapes", dict(ldo=S.T - 1, p=0, q=0), INVALID, "bad shape")]
+                         if device else []) +
+                        [("p = q = 0", dict(p=0, q=0), INVALID, "max(p, q) == 0"),
+                         ("p = q = 0 at N = 0", dict(p=0, q=0, N=0), INVALID, "max(p, q) == 0"),
+                         ("p = q = 0 before T < d", dict(p=0, q=0, d=13), INVALID, "max(p, q) == 0"),
+                         ("T < d", dict(d=13), INVALID, "T < d"),
+                         ("T < d at N = 0", dict(d=13, N=0), INVALID, "T < d"),
+                         # R = max(p, q) + max(n_future - d, 0) = 4 differenced regressor rows
+                         ("xreg_max_lag above R", dict(L=5), INVALID, "fewer differenced xreg rows than xreg_max_lag"),
+                         # R - L = 19 predictor rows, max(p, q) + T - d = 12 of history
+                         ("n_future - L above T", dict(nf=20, xs=0), INVALID, "more predictor rows than history")],
+                        overlap=RG_OVERLAP,
+                        # T = 0 passes the forecast's shapes only with n_future <= xreg_max_lag
+                        zero=[dict(T=0, d=0, nf=1)]))
     return out
 
 
@@ -273,7 +380,7 @@ SPECS = [
           ("max_d > 16", dict(max_d=17), UNSUPPORTED, AF_UNSUPPORTED),
           ("N < 0", dict(N=-1), INVALID, "bad shape"), ("T < 0", dict(T=-1), INVALID, "bad shape"),
           ("ld < T", dict(ld=S.T - 1), INVALID, "bad shape")], null=(INVALID, "bad shape")),
-] + _effects_specs() + _diag_specs() + _model_specs() + _regress_specs()
+] + _effects_specs() + _diag_specs() + _model_specs() + _regress_specs() + _regarima_specs() + _arimax_specs()
 
 
 def rows_of(sp):
@@ -556,9 +663,39 @@ def fam_regress(e, N):
         assert _same(got["stat"], np.array([r[1] for r in ref])) and _p_close(got["pvalue"], [r[2] for r in ref])
 
 
+def _xreg(N, rows):
+    return np.random.default_rng(20261021).standard_normal((5, rows, RG.k))[:N]
+
+
+def fam_regarima(e, N):
+    s, _ = _data(N)
+    x = _xreg(N, S.T)
+    coef, rho, n_iter, status = CO.fit_batch(s, x, 5)[:4]
+    got = e.regarima_co_fit(s, x, 5)
+    assert np.all(got["status"] == RR.ST_OK) and np.array_equal(got["status"], status)
+    assert np.array_equal(got["n_iter"], n_iter) and _same(got["rho"], rho) and _same(got["coef"], np.array(coef))
+
+
+def fam_arimax(e, N):
+    s, _ = _data(N)
+    x, xf = _xreg(N, S.T), _xreg(N, S.nf)
+
+    def cols(m):
+        return m.transpose(0, 2, 1).tolist()
+
+    for d in (0, 1):
+        ref = AXR.arimax_fit_batch(s, cols(x), AX.p, d, AX.q, AX.L, True, True, smear=e.get_option("smear"))
+        got = e.arimax_fit(s, x, AX.p, d, AX.q, AX.L, True, True)
+        assert ref["coef"].shape == (N, AX.Kp) and _same(got["coef"], ref["coef"]) and _same(got["ll"], ref["ll"])
+        assert all(np.array_equal(got[k], ref[k]) for k in ("status", "n_eval", "n_grad"))
+        coef = np.where(np.isnan(ref["coef"]), 0.1, ref["coef"])
+        assert _same(e.arimax_forecast(s, xf, AX.p, d, AX.q, AX.L, True, True, coef),
+                     AXR.arimax_forecast_batch(s, cols(xf), AX.p, d, AX.q, AX.L, True, True, coef))
+
+
 FAMILIES = [fam_difference, fam_css_loglik, fam_css_gradient, fam_hannan_rissanen, fam_model_flags, fam_forecast,
             fam_effects, fam_diagnostics, fam_residual_diagnostics, fam_order_search, fam_autofit, fam_kpss,
-            fam_model_fit, fam_model_eval, fam_model_effects, fam_regress]
+            fam_model_fit, fam_model_eval, fam_model_effects, fam_regress, fam_regarima, fam_arimax]
 
 
 @pytest.fixture
@@ -579,9 +716,17 @@ def test_different_staging_tables_back_to_back(fresh):
     s, c = _data(5)
     exp_diag, exp_ewma = diag_ref(_resid(s, c), S.lag), _ewma_exp(s)
     exp_fc = np.stack(_each(lambda r, k: O.forecast(r, S.p, S.d, S.q, 1, k, S.nf), s, c))
+    x = _xreg(5, S.T)
+    exp_co = CO.fit_batch(s, x, 5)
+    exp_ax = AXR.arimax_fit_batch(s, x.transpose(0, 2, 1).tolist(), AX.p, AX.d, AX.q, AX.L, True, True,
+                                  smear=fresh.get_option("smear"))
     for _ in range(2):
         diag_check(fresh.residual_diagnostics(s, S.p, S.d, S.q, True, c, S.lag), exp_diag, "sequence")
+        ax = fresh.arimax_fit(s, x, AX.p, AX.d, AX.q, AX.L, True, True)                     # 8 staged arrays
+        assert _same(ax["coef"], exp_ax["coef"]) and np.array_equal(ax["n_eval"], exp_ax["n_eval"])
         _check_ewma(fresh.ewma_fit_batch(s), exp_ewma)
+        co = fresh.regarima_co_fit(s, x, 5)                                                 # 6
+        assert _same(co["coef"], np.array(exp_co[0])) and np.array_equal(co["n_iter"], exp_co[2])
         assert _same(fresh.forecast(s, S.p, S.d, S.q, True, c, S.nf), exp_fc)
 
 

@@ -1,5 +1,6 @@
 """The host path's sizing arithmetic (spark-timeseries_amd/csrc/host_plan.hpp: chunk schedule of arima_fit_batch, the
-pinned-staging layout, par_memcpy and its partition, the fit- and diag-slice rows) swept on the CPU by
+pinned-staging layout, par_memcpy and its partition, the fit- and diag-slice rows, the extent of a strided buffer and
+the entry points' buffer table against find_overlap on hand-built lists) swept on the CPU by
 tests/sim/hostplan_sim.cpp: no chunk above min(host_chunk, N) (the schedule it replaced planned 16384-series tail
 chunks into buffers of 8193..16383 series), plans identical to that schedule wherever it stayed in bounds, staging
 regions aligned and disjoint, exact copies with untouched sentinels. Once plain, once under AddressSanitizer + UBSan
