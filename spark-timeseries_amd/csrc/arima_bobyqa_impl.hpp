@@ -17,6 +17,7 @@
 
 #include "arima_device.hpp"
 #include "arima_launch.hpp"
+#include "gen_lane.hpp"
 
 namespace sts {
 
@@ -60,7 +61,7 @@ __device__ __forceinline__ void bq_sync() {        // uniform LDS writes before 
 // p, q <= 5: the operations of css_pass in the same order (dest = 0 + I * c0, + AR lags, + MA terms; the ascending
 // maTerms copy leaves [e_{t-1}, e_{t-2}, e_{t-2}, ...]; css folded left; Int -n/2)
 __device__ double bq_css_ll(const double *__restrict__ row, int n, int p, int q, int I, const double *c) {
-    if (p > 5 || q > 5) {                          // the runtime-order path's recursion (arima_device.hpp gen_css)
+    if (p > 5 || q > 5) {                          // the runtime-order path's recursion (gen_lane.hpp gen_css)
         double cg[BQ_KMAX];
         for (int j = 0; j < BQ_KMAX; ++j) cg[j] = (j < I + p + q) ? c[j] : 0.0;
         return css_to_loglik(gen_css(GRow{row, 0}, n, p, q, I, cg), n);

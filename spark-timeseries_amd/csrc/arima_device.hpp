@@ -1053,119 +1053,6 @@ __device__ __forceinline__ void fit_prep(const FitPrep &fp) {
     for (int64_t i = g; i < fp.xready_words; i += stride) fp.xready[i] = 0u;
 }
 
-// the runtime-order path's optimizer lane (arima_generic.hip): kGenMaxK padded coordinates, the first kdim real
-using GenLane = CGLane<kGenMaxK, 0, 0, true, RuntimeDim>;
-static_assert(sizeof(GenLane) == 8 + 8 * lane_doubles<kGenMaxK, 0, 0>() + 24, "the lane's size (cg_lane.hpp), after kdim");
-
-// ---- runtime-order helpers (arima_generic.hip; css-bobyqa at orders above the compiled ones) -------------------
-// a differenced row: element i = raw[i + 1] - raw[i] (dd = 1, fused differencing) or y[i] (dd = 0)
-struct GRow {
-    const double *y;
-    int dd;
-    __device__ __forceinline__ double at(int i) const { return drow_at(y, dd, i); }
-};
-
-// ---- logLikelihoodCSSARMA's sum of squares (ARIMA.scala:430-445, iterateARMA :581-618, updateMAErrors :544-554) ----
-// c has at least one entry (the intercept term multiplies c[0] even when I = 0, as css_pass does with its padded c)
-__device__ double gen_css(const GRow &r, int n, int p, int q, int I, const double *c) {
-    const int M = p > q ? p : q;
-    double e1 = 0.0, e2 = 0.0, css = 0.0;
-    const double yh0 = 0.0 + (double)I * c[0];                       // :600
-    for (int t = M; t < n; ++t) {
-        double yh = yh0;
-        for (int j = 0; j < p; ++j) yh = yh + r.at(t - 1 - j) * c[I + j];               // :602-605
-        for (int j = 0; j < q; ++j) yh = yh + (j == 0 ? e1 : e2) * c[I + p + j];        // :608-611 (ascending copy)
-        const double e = r.at(t) - yh;                                                  // :613
-        css = css + e * e;                                                              // :440-442
-        e2 = e1;
-        e1 = e;
-    }
-    return css;
-}
-
-// ---- gradientlogLikelihoodCSSARMA (ARIMA.scala:465-534) at runtime orders; returns the css at the same point ----
-// k: the columns of dEdTheta, `coefficients.length`: I + p + q for ARIMA; ARIMAX's copy of the function
-// (ARIMAX.scala:301-370) has 1 + p + q + nX, of which only the first I + p + q are ever fed (the others receive
-// 0 - theta * 0 and 0 * error: -0.0, or NaN at a non-finite point).
-// dE: (rows x k) scratch, rows = 2 under the Breeze smear (every lag row holds the previous row 0) and
-// q + 1 under the row-shift reading. g[0..k): the gradient, already divided by -sigma2 (:532).
-__device__ double gen_grad(const GRow &r, int n, int p, int q, int I, int k, const double *c, int smear, double *g,
-                           double *dE) {
-    const int M = p > q ? p : q;
-    const int rows = smear ? (q > 0 ? 2 : 1) : q + 1;
-    for (int j = 0; j < rows * k; ++j) dE[j] = 0.0;
-    for (int j = 0; j < k; ++j) g[j] = 0.0;
-    double e1 = 0.0, e2 = 0.0, sigma2 = 0.0, css = 0.0;
-    const double nd = (double)n;
-    const double yh0 = 0.0 + (double)I * c[0];
-    for (int t = M; t < n; ++t) {
-        for (int j = 0; j < k; ++j)                                                     // :492-499
-            for (int kk = 0; kk < q; ++kk) dE[j] = dE[j] - c[I + p + kk] * dE[(smear ? 1 : kk + 1) * k + j];
-        double yh = yh0;                                                                // :502
-        if (k > 0) dE[0] = dE[0] - (double)I;                                           // :503
-        for (int j = 0; j < p; ++j) {                                                   // :506-510
-            const double v = r.at(t - 1 - j);
-            yh = yh + v * c[I + j];
-            dE[I + j] = dE[I + j] - v;
-        }
-        for (int j = 0; j < q; ++j) {                                                   // :514-518
-            const double mj = (j == 0 ? e1 : e2);
-            yh = yh + mj * c[I + p + j];
-            dE[I + p + j] = dE[I + p + j] - mj;
-        }
-        const double e = r.at(t) - yh;                                                  // :520
-        const double e_sq = e * e;
-        sigma2 = sigma2 + e_sq / nd;                                                    // :521
-        css = css + e_sq;
-        e2 = e1;                                                                        // :522
-        e1 = e;
-        for (int j = 0; j < k; ++j) g[j] = g[j] + dE[j] * e;                            // :524
-        if (smear) {                                                                    // :526, ascending element copy
-            if (q > 0)
-                for (int j = 0; j < k; ++j) dE[k + j] = dE[j];
-        } else {                                                                        // :526, row shift
-            for (int rr = q; rr >= 1; --rr)
-                for (int j = 0; j < k; ++j) dE[rr * k + j] = dE[(rr - 1) * k + j];
-        }
-        for (int j = 0; j < k; ++j) dE[j] = 0.0;                                        // :528
-    }
-    for (int j = 0; j < k; ++j) g[j] = g[j] / -sigma2;                                  // :532
-    return css;
-}
-
-// ---- ARIMAModel.isStationary / isInvertible (ARIMA.scala:777-815): the step-down of model_flags<P, Q, I> ----------
-__device__ bool gen_roots_outside(const double *poly, int N) {
-    double a[kGenMaxOrder + 1], b[kGenMaxOrder + 1];
-    for (int i = 0; i <= N; ++i) {
-        a[i] = poly[i];
-        if (!finite(a[i])) return false;
-    }
-    for (int mm = N; mm >= 1; --mm) {
-        const double kk = a[mm];
-        if (!(fabs(kk) < 1.0)) return false;
-        const double den = 1.0 - kk * kk;
-        for (int i = 0; i <= N; ++i) b[i] = (i < mm) ? (a[i] - kk * a[mm - i]) / den : 0.0;
-        for (int i = 0; i <= N; ++i) a[i] = b[i];
-    }
-    return true;
-}
-
-__device__ uint8_t gen_model_flags(const double *c, int p, int q, int I) {
-    double poly[kGenMaxOrder + 1];
-    bool st = true, inv = true;
-    if (p > 0) {
-        poly[0] = 1.0;
-        for (int j = 0; j < p; ++j) poly[1 + j] = -1.0 * c[I + j];
-        st = gen_roots_outside(poly, p);
-    }
-    if (q > 0) {
-        poly[0] = 1.0;
-        for (int j = 0; j < q; ++j) poly[1 + j] = c[I + p + j];
-        inv = gen_roots_outside(poly, q);
-    }
-    return (uint8_t)((st ? ARIMA_FLAG_STATIONARY : 0) | (inv ? ARIMA_FLAG_INVERTIBLE : 0));
-}
-
 // ------------------------------------------------------------------------------------------------------
 // Philox4x32-10 (counter-based) + Box-Muller for the synthetic generator
 // ------------------------------------------------------------------------------------------------------

@@ -260,7 +260,7 @@ struct arima_handle {
     FitCtx fctx[kMaxPipeline];
     // device workspaces of the building blocks
     DevBuf diff;
-    DevBuf fc_ws;                  // the runtime-order forecast's per-series arrays (forecast_any)
+    DevBuf fc_ws;                  // the runtime-order forecast's per-series arrays (forecast_slices)
     // the staged arrays of the host-buffer entry points, one call's at a time (CallFrame::stage)
     DevBuf staging;
     // order search: the differenced series per d, the concurrent fit lanes
@@ -518,6 +518,17 @@ class CallFrame {
     Buf buf_[sts::plan::kMaxBufs];
     size_t off_[sts::plan::kMaxBufs];
 };
+
+// The workspace forecasts (k_gen_forecast, k_arimax_gen_forecast) over N series of w workspace doubles each: slices of
+// at most 2^27 doubles (1 GiB) of h->fc_ws, at least one series; launch(f, m, ws) runs series [f, f + m) on the stream
+// of the call, where a slice's kernel ends before the next one's starts
+template <class Launch>
+int forecast_slices(arima_handle *h, int64_t N, int64_t w, const char *what, Launch launch) {
+    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t(1) << 27) / std::max<int64_t>(w, 1)));
+    RCCHK(h, h->fc_ws.ensure((size_t)std::min(chunk, N) * w * sizeof(double)), "forecast workspace");
+    for (int64_t f = 0; f < N; f += chunk) RCCHK(h, launch(f, std::min(chunk, N - f), h->fc_ws.as<double>()), what);
+    return ARIMA_OK;
+}
 
 }  // namespace
 
@@ -1392,20 +1403,16 @@ int arima_model_flags_batch(arima_handle *h, const double *coef, int64_t N, int3
 }
 
 // ARIMAModel.forecast over a device batch: k_forecast (p, q <= 5, d <= 8, the streaming kernel) or the runtime-order
-// k_gen_forecast for every other order, in slices whose per-series arrays fit a bounded workspace (h->fc_ws)
+// k_gen_forecast for every other order
 static int forecast_any(arima_handle *h, const double *ts, int64_t ld, const double *coef, int k, double *out,
                         int64_t ld_out, int64_t N, int T, int p, int d, int q, int I, int n_future, hipStream_t s) {
     if (!sts::gen_order(p, q) && d <= 8)
         return sts::launch_forecast(ts, ld, coef, k, out, ld_out, N, T, p, d, q, I, n_future, s);
     const int64_t w = sts::gen_forecast_ws_doubles(T, p, d, q, n_future);
-    const int64_t chunk = std::max<int64_t>(64, std::min<int64_t>(N, (int64_t(1) << 27) / std::max<int64_t>(w, 1)));
-    RCCHK(h, h->fc_ws.ensure((size_t)std::min(chunk, N) * w * sizeof(double)), "forecast workspace");
-    for (int64_t f = 0; f < N; f += chunk) {
-        const int64_t n = std::min(chunk, N - f);
-        RCCHK(h, sts::launch_gen_forecast(ts + f * ld, ld, coef + f * k, k, out + f * ld_out, ld_out, n, T, p, d, q, I,
-                                          n_future, h->fc_ws.as<double>(), w, s), "forecast");
-    }
-    return ARIMA_OK;
+    return forecast_slices(h, N, w, "forecast", [&](int64_t f, int64_t m, double *ws) {
+        return sts::launch_gen_forecast(ts + f * ld, ld, coef + f * k, k, out + f * ld_out, ld_out, m, T, p, d, q, I,
+                                        n_future, ws, w, s);
+    });
 }
 
 // From here on the two flavours of an operation share one body (the ARIMA effects pair excepted): the host flavour is
@@ -2018,16 +2025,10 @@ int arimax_forecast_dev(arima_handle *h, const AxShape &a, const double *ts, int
         return sts::launch_arimax_forecast_stream(ts, ld, x, xs, a.k, coef, Kp, out, ld_out, N, a.T, a.p, a.d, a.q, a.I,
                                                   a.L, a.orig, n_future, s);
     const int64_t w = sts::arimax_forecast_ws_doubles(a.T, a.p, a.d, a.q, n_future);
-    // slices of at most 1 GiB of workspace, at least one series
-    const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(N, (int64_t(1) << 27) / std::max<int64_t>(w, 1)));
-    RCCHK(h, h->fc_ws.ensure((size_t)std::min(chunk, N) * w * sizeof(double)), "forecast workspace");
-    for (int64_t f = 0; f < N; f += chunk) {
-        const int64_t m = std::min(chunk, N - f);
-        RCCHK(h, sts::launch_arimax_forecast(ts + f * ld, ld, x + f * xs, xs, a.k, coef + f * Kp, Kp, out + f * ld_out,
-                                             ld_out, m, a.T, a.p, a.d, a.q, a.I, a.L, a.orig, n_future,
-                                             h->fc_ws.as<double>(), w, s), "arimax forecast");
-    }
-    return ARIMA_OK;
+    return forecast_slices(h, N, w, "arimax forecast", [&](int64_t f, int64_t m, double *ws) {
+        return sts::launch_arimax_forecast(ts + f * ld, ld, x + f * xs, xs, a.k, coef + f * Kp, Kp, out + f * ld_out,
+                                           ld_out, m, a.T, a.p, a.d, a.q, a.I, a.L, a.orig, n_future, ws, w, s);
+    });
 }
 }  // namespace
 

@@ -205,3 +205,41 @@ def forecast_case(shape):
     coef[10, 0] = -np.inf
     ref = AX.arimax_forecast_batch(y, x_columns(x), p, d, q, L, orig, icpt, coef)
     return y, x, coef, ref
+
+
+# ---- a forecast batch larger than one workspace slice ---------------------------------------------------------------
+def forecast_ws(T, d, M, n_future):
+    """Doubles of workspace per series of the runtime-order ARIMAX forecast (csrc: arimax_forecast_ws_doubles)."""
+    n = T - d
+    hist_len, fl, tn = M + n, n_future + M, max(T, n_future)
+    return (2 * (tn + 1) + 2 * (hist_len + 1) + (fl + 1) + (d + 1) * T + 2 * (d + n_future + 1)
+            + (T + n_future + 1) + (n_future + 1) + (fl + 1))
+
+
+def forecast_slice(N, T, p, d, q, n_future):
+    """Series per launch of the workspace kernel (arima_runtime.cpp): max(1, min(N, 2^27 / w))."""
+    return max(1, min(N, (1 << 27) // max(forecast_ws(T, d, max(p, q), n_future), 1)))
+
+
+# d = 9 takes the workspace kernel at any p, q; nFuture above d, or no predictor row exists and x is never read
+SLICE_SHAPE = (512, 13, 9, (True, 1, True), (1, 1), 2)         # T, nFuture, d, (includeOriginal, L, intercept), (p, q), k
+SLICE_N = (1 << 27) // forecast_ws(512, 9, 1, 13) + 65
+SLICE_WINDOW = 64                                                # rows on each side of the boundary forecast alone
+SLICE_REF = 4                                                    # rows on each side held to the restatement
+
+
+@functools.lru_cache(maxsize=None)
+def slice_case():
+    """(series N x T, x N x nFuture x k, coef N x K', sl, restated forecasts of rows [sl - 4, sl + 4)): one matrix and
+    one model per series, every row drawn on its own, so rows a slice apart differ in all three."""
+    T, nF, d, (orig, L, icpt), (p, q), k = SLICE_SHAPE
+    rng = np.random.default_rng(271828)
+    y = np.cumsum(rng.standard_normal((SLICE_N, T)), axis=1) + 10.0
+    x = rng.standard_normal((SLICE_N, nF, k)) + 3.0
+    coef = rng.uniform(-0.5, 0.5, (SLICE_N, AX.num_coef(k, p, q, L, orig)))
+    sl = forecast_slice(SLICE_N, T, p, d, q, nF)
+    r = slice(sl - SLICE_REF, sl + SLICE_REF)
+    ref = AX.arimax_forecast_batch(y[r], x_columns(x[r]), p, d, q, L, orig, icpt, coef[r])
+    for a in (y, x, coef, ref):
+        a.setflags(write=False)
+    return y, x, coef, sl, ref

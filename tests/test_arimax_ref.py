@@ -293,3 +293,26 @@ def test_device_forecast_inputs():
     again = AX.arimax_forecast_batch(y, C.x_columns(clean), s[4][0], s[2], s[4][1], s[3][1], s[3][0], s[3][2], coef)
     assert _bits(again[~np.isnan(ref)]) == _bits(ref[~np.isnan(ref)]) and np.array_equal(np.isnan(again), np.isnan(ref))
     assert not np.any(np.isnan(ref[:7])) and np.all(np.isnan(ref[9, -1:])) and not np.any(np.isnan(ref[7]))
+
+
+def test_device_forecast_slice_inputs():
+    T, nF, d, (orig, L, icpt), (p, q), k = C.SLICE_SHAPE
+    assert d > 8 and nF > d                                  # the workspace kernel, with predictor rows to read
+    AX.forecast_check(T, k, nF, p, d, q, L)
+    assert C.forecast_ws(T, d, max(p, q), nF) == 7772
+    y, x, coef, sl, ref = C.slice_case()
+    N = C.SLICE_N
+    assert sl == 17269 and sl < N < 2 * sl and C.SLICE_WINDOW <= N - sl
+    assert ref.shape == (2 * C.SLICE_REF, T) and np.isfinite(ref).all()
+    # rows a slice apart differ everywhere, in every array the second launch offsets
+    for a in (y, x, coef):
+        assert not np.any(a[sl:] == a[:N - sl])
+    # and each offset shows on its own: the first row of the second slice with one array taken a slice earlier
+    i, want = sl, ref[C.SLICE_REF]
+
+    def fc(ts, xm, c):
+        return np.array(AX.arimax_forecast(ts, C.x_columns(xm), p, d, q, L, orig, icpt, c))
+
+    assert _bits(fc(y[i], x[i], coef[i])) == _bits(want)
+    assert not np.any(fc(y[0], x[i], coef[i]) == want)
+    assert _bits(fc(y[i], x[0], coef[i])) != _bits(want) and _bits(fc(y[i], x[i], coef[0])) != _bits(want)

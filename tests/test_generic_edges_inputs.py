@@ -210,7 +210,7 @@ def test_stride_batch_is_past_the_grid_and_mostly_converges():
 
 # ---- 3. forecast slices -------------------------------------------------------------------------------------------
 def gen_forecast_ws(T, d, M, n_future):
-    """Doubles of workspace per series of the runtime-order forecast (arima_generic.hip gen_forecast_ws)."""
+    """Doubles of workspace per series of the runtime-order forecast (gen_lane.hpp GenFcLayout<false>)."""
     n = T - d
     hist_len = M + n
     fl = n_future + M
@@ -218,9 +218,9 @@ def gen_forecast_ws(T, d, M, n_future):
 
 
 def forecast_slice(N, T, p, d, q, n_future):
-    """Series per launch of forecast_any (arima_runtime.cpp): max(64, min(N, 2^27 / w))."""
+    """Series per launch of the workspace kernel (arima_runtime.cpp forecast_slices): max(1, min(N, 2^27 / w))."""
     w = gen_forecast_ws(T, d, max(p, q), n_future)
-    return max(64, min(N, (1 << 27) // max(w, 1)))
+    return max(1, min(N, (1 << 27) // max(w, 1)))
 
 
 SLICE_ORDER, SLICE_T, SLICE_NF = (6, 16, 1, 1), 512, 5

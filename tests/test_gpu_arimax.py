@@ -147,6 +147,37 @@ def test_forecast_bit_parity(engine, shape):
     assert _same(shared, AX.arimax_forecast_batch(y[:3], C.x_columns(x[1]), p, d, q, Lx, orig, icpt, coef[2]))
 
 
+def test_forecast_workspace_slices(engine):
+    """More series than one slice of the forecast workspace: the second launch starts inside the batch, at series sl,
+    with the series, the regressors, the coefficients and the output each offset by their own stride."""
+    import torch
+    T, nF, d, (orig, Lx, icpt), (p, q), k = C.SLICE_SHAPE
+    y, x, coef, sl, ref = C.slice_case()
+    N, W, R4 = C.SLICE_N, C.SLICE_WINDOW, C.SLICE_REF
+    assert sl < N < 2 * sl                                   # a second launch, or the test tests nothing
+    win = slice(sl - W, sl + W)
+    whole = engine.arimax_forecast(y, x, p, d, q, Lx, orig, icpt, coef)
+    assert whole.shape == (N, T)
+    alone = engine.arimax_forecast(y[win], x[win], p, d, q, Lx, orig, icpt, coef[win])
+    assert _same(whole[win], alone)
+    assert _same(whole[sl - R4:sl + R4], ref)
+    # the device entry: strided rows and matrices (NaN padding behind each), a strided output with guard columns
+    ld, xs, ld_out = T + 3, k * nF + 3, T + 5
+    buf = torch.full((N, ld), float("nan"), dtype=torch.float64, device="cuda")
+    buf[:, :T] = torch.tensor(y, device="cuda")
+    dx = torch.full((N, xs), float("nan"), dtype=torch.float64, device="cuda")
+    dx[:, :k * nF] = torch.tensor(np.ascontiguousarray(x.transpose(0, 2, 1)).reshape(N, k * nF), device="cuda")
+    dcoef = torch.tensor(coef, device="cuda")
+    dout = torch.full((N, ld_out), -7.0, dtype=torch.float64, device="cuda")
+    engine.arimax_forecast_device(buf.data_ptr(), N, T, ld, dx.data_ptr(), xs, k, nF, p, d, q, Lx, orig, icpt,
+                                  dcoef.data_ptr(), dout.data_ptr(), ld_out)
+    got = dout.cpu().numpy()
+    assert np.all(got[:, T:] == -7.0), np.argwhere(got[:, T:] != -7.0)[:4]
+    assert _same(got[win, :T], alone) and _same(got[sl - R4:sl + R4, :T], ref)
+    assert _same(got[:, :T], whole)
+    assert torch.isnan(buf[:, T:]).all() and torch.isnan(dx[:, k * nF:]).all()
+
+
 def test_forecast_invalid_shapes(engine):
     y, coef = np.ones((2, 40)), np.full((2, 41), 0.1)
 
